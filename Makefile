@@ -10,8 +10,8 @@ test-cpu: build   ## oracle vs goldens, host logic, ABI symbols, gloo world size
 test-gpu:         ## parity through the C ABI on an MI355X
 	python -m pytest tests -x -q -m gpu
 
-bench:            ## one JSON line
-	python bench.py
+bench:            ## one JSON line with every leg; the headline alone: python bench.py
+	python bench.py --full
 
 round:            ## on a GPU box: tests, smoke, bench, regimes, C5, rocprofv3 + PMC passes -> gpurun_out/
 	bash tools/gpu_round.sh

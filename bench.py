@@ -37,6 +37,12 @@ Beside it: the reference's arithmetic without its thread pools and cache lookups
 o1.py:204-213 scoring on Python int lists (oracle/pybaseline.py) -- on one host core and on a process pool, and the C
 restatement (oracle/scv_oracle.c).  The same leg is the checker: GPU cells of a timed chunk vs the C oracle (>= 256 problems x 8 budgets x
 2^20 votes) and vs the Python reference arithmetic.  It is the ONLY place bench.py touches oracle/.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line.  --full adds everything else the
+line can carry, each outside the timed region: the cpu_baseline leg and its parity checks (every rank's oracle check when N > 1, the
+bootstrap check of c5), c3_full, the live read ceiling and the live roofline.traffic.  --dump-outputs DIR writes what the timed path
+returned in its last timed step (packed counters, the decoded cell table, cell tokens, c5's resample table) as DIR/<name>.npy in float64,
+so that two builds can be compared output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -56,6 +62,9 @@ if REPO not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 BYTES_PER_VOTE = 4             # one int32 read per sample-vote, nothing written per vote
+# the headline's name, the same in every run of the timed path; whether THIS run compared its outputs with the C oracle is in `parity`
+METRIC = "sample-votes/sec (problems x samples), bit-exact vs CPU (see parity)"
+PARITY_NOT_CHECKED = "not checked in this run: with --full, bench.py compares the last timed chunk with oracle/scv_oracle.c"
 DISTS = {0: "D0 uniform", 1: "D1 peaked", 2: "D2 degenerate", 3: "D3 tie", 4: "D4 peaked on a wrong value", 5: "D5 degenerate-wrong"}
 
 
@@ -74,8 +83,8 @@ def parse():
     ap.add_argument("--resident", type=int, default=0,
                     help="distinct chunks kept in HBM and cycled (0 = auto: c3 as many of its 8 chunks as fit in free HBM)")
     ap.add_argument("--tokens", action="store_true", help="also stream the tokens tensor (8 B/vote)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-read-ceiling", action="store_true", help="skip the pure-read probe after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg and the oracle checks (always skipped without --full)")
+    ap.add_argument("--no-read-ceiling", action="store_true", help="with --full: skip the pure-read probe after the timed region (always skipped without --full)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=5.0, help="single-core Python reference arithmetic")
     ap.add_argument("--parity-problems", type=int, default=256, help="problems of the last timed chunk checked vs the C oracle")
     ap.add_argument("--copies", type=int, default=0)
@@ -100,12 +109,46 @@ def parse():
                     help="TEST ONLY: every rank uses cuda:0 (1-GPU box, with --backend gloo) to exercise the multi-process path")
     ap.add_argument("--dump", default=None, help="rank 0 writes the last step's integer outputs (.npz) for bit-exact comparisons")
     ap.add_argument("--full-pass", dest="full_pass", action="store_true", default=True,
-                    help="c3 on ONE GPU (default on): after the timed region, aggregate ALL 8 chunks of the workload (the 8th is generated into a "
+                    help="c3 on ONE GPU, with --full (on there by default; a run without --full never does it): after the timed region, aggregate ALL 8 chunks of the workload (the 8th is generated into a "
                          "freed slot) into one counter buffer and print c3_full = C3's RESULT (accuracy per budget, sums, sha256 of the counters)")
     ap.add_argument("--no-full-pass", dest="full_pass", action="store_false")
     ap.add_argument("--no-live-traffic", dest="live_traffic", action="store_false", default=True,
-                    help="default c3 run on one GPU: do not re-run the command under rocprofv3 --pmc for roofline.traffic (the committed profiles/ figure is quoted instead)")
-    return ap.parse_args()
+                    help="default c3 run on one GPU with --full: do not re-run the command under rocprofv3 --pmc for roofline.traffic (the committed "
+                         "profiles/ figure is quoted instead, as in every run without --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: cpu_baseline and parity checks, c3_full, the live read ceiling and roofline.traffic "
+                         "(the --no-* options above switch single legs off again)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.full_pass, args.no_read_ceiling, args.live_traffic = True, False, True, False
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (the outputs are integers below 2^53, so the values are exact).  When the
+    whole would exceed DUMP_LIMIT_BYTES, each array keeps a fixed, seeded sample of its rows along axis 0, and DIR/<name>_rows.npy says
+    which rows those are."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v).astype(np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (DUMP_LIMIT_BYTES // 2) / total))
+            rows = np.sort(np.random.default_rng(20240914).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def cell_fields(cells):
+    """The decoded cell table (CELL_DTYPE [P, B]) as one array per field, the names --dump-outputs writes."""
+    return {f"cells_{f}": cells[f] for f in ("max_count", "truth_count", "n_modes", "min_mode", "hit")}
 
 
 # ---- the cpu_baseline leg: the only code here that touches oracle/ (test infrastructure) -------------------
@@ -738,7 +781,7 @@ def main_single_process(args):
     achieved = bytes_per_launch / (kern_avg_ms * 1e-3) / 1e9
     final = AggregateResult.from_counters(last.cpu().numpy(), Pc, B, num_problems=args.problems if c5 else Pc * world)
     out = {
-        "metric": "sample-votes/sec (problems x samples)", "value": total_votes / elapsed, "unit": "sample-votes/s", "n_gpus": world,
+        "metric": METRIC, "value": total_votes / elapsed, "unit": "sample-votes/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / max(args.steps, 1) * 1e3, "higher_is_better": True,
         "scaling": "strong" if c5 else "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
         "config": {
@@ -770,9 +813,8 @@ def main_single_process(args):
         out["parity"] = (f"bit-exact: EVERY rank's first {exchange['parity_problems_per_rank']} problems x {B} budgets x {N} votes of its last timed chunk "
                          f"({world} ranks; + {n0} of rank 0's sanity pass) vs oracle/scv_oracle.c; all-reduced counters of every rank == the "
                          f"independently gathered int64 sum ({ncount} words)")
-        out["metric"] += ", bit-exact vs CPU (see parity)"
     else:
-        out["metric"] += " (parity not checked in this run)"
+        out["parity"] = PARITY_NOT_CHECKED
     if c5:
         cnt, table, boot, M = c5_state["last"]
         out["c5"] = {"tie_classes_M": M, "device_error_word": int(cnt.cpu()[ncount])}
@@ -784,8 +826,14 @@ def main_single_process(args):
             out["c5"]["bootstrap_parity"] = f"all {args.resamples} x {B} x {M} resample counters bit-exact vs oracle/scv_oracle.c"
         if args.dump:
             np.savez(args.dump, counters=cnt.cpu().numpy()[:ncount], cells=table.cpu().numpy(), boot=boot.cpu().numpy())
-    elif args.dump:
-        np.savez(args.dump, counters=last.cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(counters=cnt.cpu().numpy()[:ncount], **cell_fields(cells_from_torch(table)), boot=boot.cpu().numpy()))
+    else:
+        if args.dump:
+            np.savez(args.dump, counters=last.cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(counters=last.cpu().numpy()[:ncount], **cell_fields(last_cells),
+                                                 cell_tokens=None if ctok[0] is None else ctok[0].cpu().numpy()))
     mde.close()
     emit(out)
 
@@ -991,6 +1039,7 @@ def main():
     # the cell table now holds the LAST TIMED step's chunk (c5: this rank's shard); every rank keeps its own for the oracle
     last_cells = cells_from_torch(cells)
     last_host = None if last is None else last.cpu().numpy().copy()       # the reduced counters of the last TIMED step (the buffers are reused below)
+    last_ctok = ctok.cpu().numpy() if (args.dump_outputs and ctok is not None) else None
     if split_timing:
         eng_t = Engine(device=local_rank, timing=True)
         eng_t.set_tuning(args.copies, args.threads, args.wg_per_cu, args.unroll)
@@ -1160,7 +1209,7 @@ def main():
         workload = (f"C2: step = one pass over {Pc} problems x {B} budgets x {N} samples int32 "
                     f"({bytes_per_launch / 1e6:.1f} MB) per GPU, {R} distinct tensors cycled (cold Infinity Cache)")
     out = {
-        "metric": "sample-votes/sec (problems x samples)",
+        "metric": METRIC,
         "value": value,
         "unit": "sample-votes/s",
         "n_gpus": world,
@@ -1243,10 +1292,8 @@ def main():
             out["cpu_baseline"] = None
     elif rank == 0:
         out["cpu_baseline"] = None
-    if out["parity"]:
-        out["metric"] += ", bit-exact vs CPU (see parity)"
-    else:
-        out["metric"] += " (parity not checked in this run)"
+    if not out["parity"]:
+        out["parity"] = PARITY_NOT_CHECKED
 
     # ---- C5 epilogue (outside the timed region): gather the bootstrap slices, host floats, oracle check ----------
     if c5:
@@ -1282,8 +1329,13 @@ def main():
                 out["c5"]["bootstrap_parity"] = f"all {args.resamples} x {B} x {d.M} resample counters bit-exact vs oracle/scv_oracle.c"
             if args.dump:
                 np.savez(args.dump, counters=d.counters.cpu().numpy(), cells=d.cells.cpu().numpy(), boot=boot_all.cpu().numpy())
-    elif rank == 0 and args.dump:
-        np.savez(args.dump, counters=last_host, **({"full": full_host} if full_host is not None else {}))
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, dict(counters=d.counters.cpu().numpy()[:counters_size(B)], **cell_fields(all_cells), boot=boot_all.cpu().numpy()))
+    elif rank == 0:
+        if args.dump:
+            np.savez(args.dump, counters=last_host, **({"full": full_host} if full_host is not None else {}))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(counters=last_host[:counters_size(B)], **cell_fields(last_cells), cell_tokens=last_ctok))
     if rank == 0:
         out["warnings"] = list(WARNINGS) or None
         print(json.dumps(out), flush=True)

@@ -46,3 +46,47 @@ def test_spawn_command_is_the_drivers_own_launcher_line(monkeypatch):
     assert cmd[cmd.index("--nproc-per-node") + 1] == "4" and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-7:] == [os.path.join(REPO, "bench.py"), "--gpus", "4", "--steps", "2", "--share-device", "--backend", "gloo"][-7:]
     assert seen["env"]["SCV_BENCH_SPAWNED"] == "1"
+
+
+def test_a_plain_run_leaves_every_leg_but_the_headline_to_full(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` only sets up, warms up and times: the cpu_baseline leg with its parity checks, c3_full, the
+    live read ceiling and the live roofline.traffic run with --full alone, where the --no-* options still switch single legs off."""
+    import importlib
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module("bench")
+    legs = lambda a: (a.no_cpu_baseline, a.full_pass, a.no_read_ceiling, a.live_traffic)  # noqa: E731
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert legs(a) == (True, False, True, False) and a.steps == 5 and a.warmup == 2 and a.dump_outputs is None
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--full"])
+    assert legs(bench.parse()) == (False, True, False, True)
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--no-full-pass", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert legs(a) == (True, False, False, True) and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float64_arrays_and_a_fixed_sample_beyond_64_mb(tmp_path):
+    import importlib
+
+    import numpy as np
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module("bench")
+    counters = np.arange(8 * 1027, dtype=np.int64) * ((1 << 39) + 1)          # up to 2^52: exact in float64
+    cells = np.zeros((3, 2), dtype=[("max_count", "<u4"), ("truth_count", "<u4"), ("n_modes", "<u2"), ("min_mode", "<i2"), ("hit", "u1")])
+    cells["min_mode"] = -1
+    bench.dump_outputs(str(tmp_path / "small"), dict(counters=counters, **bench.cell_fields(cells), cell_tokens=None))
+    names = sorted(os.listdir(tmp_path / "small"))
+    assert names == ["cells_hit.npy", "cells_max_count.npy", "cells_min_mode.npy", "cells_n_modes.npy", "cells_truth_count.npy", "counters.npy"]
+    got = np.load(tmp_path / "small" / "counters.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), counters)
+    assert np.array_equal(np.load(tmp_path / "small" / "cells_min_mode.npy"), np.full((3, 2), -1.0))
+    big = np.arange(3 << 20, dtype=np.int64).reshape(-1, 8)                  # 24 MB as float64, x 4 arrays > 64 MB
+    arrays = {f"a{i}": big + i for i in range(4)}
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = sum(os.path.getsize(tmp_path / "x" / n) for n in os.listdir(tmp_path / "x"))
+    assert total <= 64 << 20
+    rows = np.load(tmp_path / "x" / "a2_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "x" / "a2.npy"), (big + 2)[rows]) and np.all(np.diff(rows) > 0)
+    for n in os.listdir(tmp_path / "x"):
+        assert np.array_equal(np.load(tmp_path / "x" / n), np.load(tmp_path / "y" / n)), n

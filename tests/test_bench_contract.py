@@ -42,7 +42,7 @@ def _bench(extra, ranks=1, timeout=900, self_spawn=False, env=None):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _bench(["--problems-per-step", "48", "--samples", str(1 << 16), "--steps", "3", "--warmup", "1", "--cpu-baseline-seconds", "0.5"])
+    d = _bench(["--problems-per-step", "48", "--samples", str(1 << 16), "--steps", "3", "--warmup", "1", "--cpu-baseline-seconds", "0.5", "--full"])
     assert KEYS <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["higher_is_better"] is True and d["vs_baseline"] is None and d["dtype"] == "int32" and d["data"] == "synthetic"
@@ -64,11 +64,34 @@ def test_single_gpu_line_has_the_contract_fields():
     assert abs(d["value"] - 48 * 8 * (1 << 16) * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-9
 
 
+def test_plain_line_is_lean_and_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """Without --full the line carries the headline and nothing that needs another measurement or check; --dump-outputs writes the last
+    timed step's counters, cell table and cell tokens in float64 -- the same in two plain runs, in a --full run and in the run's own --dump."""
+    shape = ["--problems-per-step", "48", "--samples", str(1 << 15), "--steps", "3", "--warmup", "1", "--tokens"]
+    runs = {name: _bench([*shape, *extra, "--dump-outputs", str(tmp_path / name), "--dump", str(tmp_path / f"{name}.npz")])
+            for name, extra in (("a", []), ("b", []), ("full", ["--full", "--cpu-baseline-seconds", "0.2"]))}
+    d = runs["a"]
+    assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "int32"
+    assert d["cpu_baseline"] is None and d["parity"].startswith("not checked in this run") and d["c3_full"] is None
+    assert d["metric"] == runs["full"]["metric"] == "sample-votes/sec (problems x samples), bit-exact vs CPU (see parity)"
+    assert runs["full"]["c3_full"]["problems"] == 8 * 48 and runs["full"]["parity"].startswith("bit-exact")
+    assert abs(d["value"] - 48 * 8 * (1 << 15) * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-9
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["counters.npy", "cell_tokens.npy"] + [f"cells_{f}.npy" for f in ("max_count", "truth_count", "n_modes", "min_mode", "hit")])
+    counters = np.load(tmp_path / "a" / "counters.npy")
+    assert counters.dtype == np.float64 and np.array_equal(counters.astype(np.int64), np.load(tmp_path / "a.npz")["counters"])
+    assert np.load(tmp_path / "a" / "cells_hit.npy").shape == np.load(tmp_path / "a" / "cell_tokens.npy").shape == (48, 8)
+    for name in ("b", "full"):
+        assert sorted(os.listdir(tmp_path / name)) == names
+        for n in names:
+            assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / name / n)), (name, n)
+
+
 def test_two_ranks_equal_one_rank_word_for_word(tmp_path):
     """Weak scaling: step s of a G-rank run covers global problems [s G Pc, (s+1) G Pc).  Two ranks x 48 problems must
     give the SAME all-reduced counters (8216 int64 words) as one rank x 96 problems."""
     common = ["--samples", str(1 << 15), "--steps", "3", "--warmup", "1", "--resident", "4"]
-    two = _bench(["--problems-per-step", "48", *common, "--dump", str(tmp_path / "two.npz")], ranks=2)
+    two = _bench(["--problems-per-step", "48", *common, "--full", "--dump", str(tmp_path / "two.npz")], ranks=2)
     one = _bench(["--problems-per-step", "96", *common, "--dump", str(tmp_path / "one.npz"), "--no-cpu-baseline"])
     assert two["n_gpus"] == 2 and two["cpu_baseline"] is None and two["parity"].startswith("bit-exact: EVERY rank's first 32 problems") and two["allreduce_verified"] is True and two["parity_ranks_checked"] == 2
     assert two["config"]["backend"] == "gloo" and two["config"]["devices_shared_by_ranks"] is True
@@ -82,7 +105,7 @@ def test_c5_two_ranks_equal_one_rank_and_oracle(tmp_path):
     gathered cell table and the whole bootstrap table of a 2-rank run equal the 1-rank run's, which bench.py
     itself compares with the oracle (cells + all resample counters)."""
     common = ["--workload", "c5", "--problems", "300", "--samples", str(1 << 14), "--resamples", "101", "--steps", "2", "--warmup", "1", "--dist", "3"]
-    one = _bench([*common, "--dump", str(tmp_path / "one.npz"), "--cpu-baseline-seconds", "0.3"])
+    one = _bench([*common, "--dump", str(tmp_path / "one.npz"), "--cpu-baseline-seconds", "0.3", "--full"])
     two = _bench([*common, "--dump", str(tmp_path / "two.npz"), "--no-cpu-baseline"], ranks=2)
     assert one["scaling"] == "strong" and "bootstrap_parity" in one["c5"] and one["parity"].startswith("bit-exact")
     a, b = np.load(tmp_path / "one.npz"), np.load(tmp_path / "two.npz")
@@ -126,7 +149,7 @@ def test_c2_steps_captured_in_one_graph_launch():
     """C2 (30 x 8 x 2^17, one kernel launch per evaluation): --graph --graph-steps K replays K evaluations per graph
     launch; steps round up to a multiple of K, the line keeps the contract and the cells of the last timed step are
     checked against the oracle inside bench.py."""
-    d = _bench(["--workload", "c2", "--steps", "10", "--warmup", "3", "--graph", "--graph-steps", "4", "--cpu-baseline-seconds", "0.2"])
+    d = _bench(["--workload", "c2", "--steps", "10", "--warmup", "3", "--graph", "--graph-steps", "4", "--cpu-baseline-seconds", "0.2", "--full"])
     assert KEYS <= set(d) and d["steps"] == 12 and d["warmup"] == 4
     assert d["config"]["launch"] == "hipGraph replay (4 step(s) per graph launch)"
     assert d["parity"].startswith("bit-exact: 30 problems x 8 budgets x 131072 votes of the last TIMED chunk")
@@ -139,7 +162,7 @@ def test_plain_python_bench_gpus_2_starts_its_own_ranks(tmp_path):
     itself too, o1.py:232-240) and relays exactly one JSON line.  Two self-started ranks (gloo, sharing cuda:0) must
     give the 1-rank run's counters word for word."""
     common = ["--samples", str(1 << 15), "--steps", "3", "--warmup", "1", "--resident", "4"]
-    two = _bench(["--problems-per-step", "48", *common, "--backend", "gloo", "--share-device", "--dump", str(tmp_path / "two.npz")],
+    two = _bench(["--problems-per-step", "48", *common, "--backend", "gloo", "--share-device", "--full", "--dump", str(tmp_path / "two.npz")],
                  ranks=2, self_spawn=True)
     one = _bench(["--problems-per-step", "96", *common, "--dump", str(tmp_path / "one.npz"), "--no-cpu-baseline"])
     assert two["n_gpus"] == 2 and two["steps"] == 3 and two["config"]["ranks_started_by"].startswith("bench.py itself")
@@ -159,7 +182,7 @@ def test_plain_python_bench_runs_rccl_on_a_self_started_rank(tmp_path):
     assert d["config"]["rccl_ranks"] == 1 == d["n_gpus"] and d["config"]["collectives_forced_on_one_rank"] is True
     assert d["config"]["ranks_started_by"].startswith("bench.py itself")
     assert d["config"]["hsa_enable_ipc_mode_legacy"]["source"]                   # inherited, probed, or left unset: always said
-    plain = _bench([*c3, "--dump", str(tmp_path / "plain.npz")])
+    plain = _bench([*c3, "--full", "--dump", str(tmp_path / "plain.npz")])
     assert np.array_equal(np.load(tmp_path / "rccl.npz")["counters"], np.load(tmp_path / "plain.npz")["counters"])
 
 
@@ -195,7 +218,7 @@ def test_single_process_communicator_runs_equal_the_torch_run_word_for_word(tmp_
     assert rccl["config"]["comm"] == "rccl" and rccl["config"]["rccl_ranks"] == 1 and rccl["config"]["comm_selftest_words_per_rank"] > 0
     # parity leg of the single-process line, and C5 through the communicator (cells + whole resample table vs the oracle inside bench.py)
     c5 = ["--workload", "c5", "--problems", "300", "--samples", str(1 << 14), "--resamples", "101", "--steps", "2", "--warmup", "1", "--dist", "3"]
-    p5 = _bench(["--comm", "peer", "--gpus", "3", "--share-device", *c5, "--dump", str(tmp_path / "p5.npz")])
+    p5 = _bench(["--comm", "peer", "--gpus", "3", "--share-device", *c5, "--full", "--dump", str(tmp_path / "p5.npz")])
     t5 = _bench([*c5, "--dump", str(tmp_path / "t5.npz"), "--no-cpu-baseline"])
     assert p5["parity"].startswith("bit-exact: EVERY rank's first 32 problems") and p5["allreduce_verified"] is True and p5["parity_ranks_checked"] == 3 and "bootstrap_parity" in p5["c5"] and p5["c5"]["device_error_word"] == 0
     x, y = np.load(tmp_path / "p5.npz"), np.load(tmp_path / "t5.npz")
@@ -213,7 +236,11 @@ def test_single_process_communicator_with_too_few_gpus_is_one_json_error_line():
     assert "error" in d and f"--gpus {n}" in d["error"] and d["value"] is None
 
 
-# ---- rehearsal at the target rank count: 8 ranks, P = 10 000 in shards of 1250, every stack, C3/C4 and C5 ----
+# ---- rehearsal at the target rank count: 8 ranks in ONE process over the peer communicator, P = 10 000 in shards of 1250,
+# C3/C4 and C5; the torch/gloo stack with RANK_PROCESSES rank processes over the same problems.  Where the GPU suite runs, at most 6 processes may
+# have the GPU open at once (a run with the pytest process + 8 ranks is stopped): pytest + 4 ranks stays below that ----
+
+RANK_PROCESSES = 4
 
 EIGHT = ["--samples", "256", "--steps", "2", "--warmup", "1", "--resident", "2"]
 
@@ -229,43 +256,45 @@ def _assert_self_verified(d, ranks, oracle=True):
         assert d["parity_ranks_checked"] == 0
 
 
-def test_eight_ranks_c4_shape_every_stack_equals_one_rank(tmp_path):
-    """C4's shape at the target rank count on the 1-GPU box: 8 ranks x 1250 problems per step (a 10 000-problem step), torch/gloo
-    processes and ONE process over the library's peer communicator (8 contexts on cuda:0), and single-process RCCL on one device,
-    all equal to one rank x 10 000 problems word for word -- and each multi-rank line has verified its own exchange step on EVERY
-    rank (pre-reduce counters gathered independently, numpy sum == every rank's all-reduced buffer) and sent 32 problems of EVERY
-    rank's last chunk through the oracle."""
+def test_c4_shape_on_eight_peer_ranks_and_four_rank_processes_equals_one_rank(tmp_path):
+    """C4's shape at the target rank count on the 1-GPU box: ONE process over the library's peer communicator with 8 ranks x 1250
+    problems per step (8 contexts on cuda:0; a 10 000-problem step), torch/gloo processes -- RANK_PROCESSES ranks x 2500 problems, the
+    rank processes the suite may keep on one GPU at a time -- and single-process RCCL on one device, all equal to one rank x 10 000
+    problems word for word -- and each multi-rank line has verified its own exchange step on EVERY rank (pre-reduce counters
+    gathered independently, numpy sum == every rank's all-reduced buffer) and sent 32 problems of EVERY rank's last chunk through
+    the oracle."""
     one = _bench(["--problems-per-step", "10000", *EIGHT, "--no-cpu-baseline", "--dump", str(tmp_path / "one.npz")])
     want = np.load(tmp_path / "one.npz")["counters"]
     assert want.shape == (8 * 1027,) and want.sum() > 0
-    tor = _bench(["--problems-per-step", "1250", *EIGHT, "--dump", str(tmp_path / "torch8.npz")], ranks=8)
-    assert tor["n_gpus"] == 8 and tor["config"]["backend"] == "gloo" and np.array_equal(np.load(tmp_path / "torch8.npz")["counters"], want)
-    _assert_self_verified(tor, 8)
-    peer = _bench(["--comm", "peer", "--gpus", "8", "--share-device", "--problems-per-step", "1250", *EIGHT, "--dump", str(tmp_path / "peer8.npz")])
+    tor = _bench(["--problems-per-step", str(10000 // RANK_PROCESSES), *EIGHT, "--full", "--dump", str(tmp_path / "torch4.npz")], ranks=RANK_PROCESSES)
+    assert tor["n_gpus"] == RANK_PROCESSES and tor["config"]["backend"] == "gloo" and np.array_equal(np.load(tmp_path / "torch4.npz")["counters"], want)
+    _assert_self_verified(tor, RANK_PROCESSES)
+    peer = _bench(["--comm", "peer", "--gpus", "8", "--share-device", "--problems-per-step", "1250", *EIGHT, "--full", "--dump", str(tmp_path / "peer8.npz")])
     assert peer["n_gpus"] == 8 and peer["config"]["devices"] == [0] * 8 and np.array_equal(np.load(tmp_path / "peer8.npz")["counters"], want)
     _assert_self_verified(peer, 8)
-    rccl = _bench(["--comm", "rccl", "--gpus", "1", "--problems-per-step", "10000", *EIGHT, "--dump", str(tmp_path / "rccl1.npz")])
+    rccl = _bench(["--comm", "rccl", "--gpus", "1", "--problems-per-step", "10000", *EIGHT, "--full", "--dump", str(tmp_path / "rccl1.npz")])
     assert np.array_equal(np.load(tmp_path / "rccl1.npz")["counters"], want) and rccl["config"]["rccl_ranks"] == 1
     _assert_self_verified(rccl, 1)
     assert tor["accuracy_last_step"] == peer["accuracy_last_step"] == rccl["accuracy_last_step"] == one["accuracy_last_step"]
 
 
-def test_eight_ranks_c5_every_stack_equals_one_rank(tmp_path):
-    """C5 at the target rank count: P = 10 000 in shards of 1250, R = 1000 resamples = 125 per rank; counters, the gathered
-    cell table and the whole resample table of the 8-rank runs (torch/gloo processes; one process, peer communicator) equal
-    the 1-rank run's, which bench.py compares with the oracle; every rank verified its gathered tables."""
-    c5 = ["--workload", "c5", "--problems", "10000", "--samples", "256", "--resamples", "1000", "--steps", "2", "--warmup", "1", "--dist", "3"]
+def test_c5_on_eight_peer_ranks_and_four_rank_processes_equals_one_rank(tmp_path):
+    """C5 at the target rank count: P = 10 000 in shards of 1250, R = 1000 resamples = 125 per rank, in ONE process over the peer
+    communicator (8 contexts), and in shards of 2500 with 250 resamples per rank over 4 torch/gloo processes (as many rank processes
+    as the suite may keep on one GPU at a time); counters, the gathered cell table and the whole resample table of the multi-rank runs
+    equal the 1-rank run's, which bench.py compares with the oracle; every rank verified its gathered tables."""
+    c5 = ["--workload", "c5", "--problems", "10000", "--samples", "256", "--resamples", "1000", "--steps", "2", "--warmup", "1", "--dist", "3", "--full"]
     one = _bench([*c5, "--dump", str(tmp_path / "one.npz"), "--cpu-baseline-seconds", "0.3"])
     assert "bootstrap_parity" in one["c5"]
-    tor = _bench([*c5, "--dump", str(tmp_path / "t8.npz")], ranks=8)
+    tor = _bench([*c5, "--dump", str(tmp_path / "t4.npz")], ranks=RANK_PROCESSES)
     peer = _bench(["--comm", "peer", "--gpus", "8", "--share-device", *c5, "--dump", str(tmp_path / "p8.npz")])
     a = np.load(tmp_path / "one.npz")
-    for name in ("t8", "p8"):
+    for name in ("t4", "p8"):
         b = np.load(tmp_path / f"{name}.npz")
         for k in ("counters", "cells", "boot"):
             assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), (name, k)
     assert a["boot"].shape[0] == 1000 and a["cells"].shape[:2] == (10000, 1)
-    _assert_self_verified(tor, 8)
+    _assert_self_verified(tor, RANK_PROCESSES)
     _assert_self_verified(peer, 8)
     assert tor["exchange_check"]["c5_resample_table_equal_on_every_rank"] is True
     assert "bootstrap_parity" in tor["c5"] and "bootstrap_parity" in peer["c5"]
@@ -275,9 +304,9 @@ def test_eight_ranks_c5_every_stack_equals_one_rank(tmp_path):
 def test_multi_rank_line_checks_the_closed_form_of_the_degenerate_distribution():
     """--dist 2: every cell is a strict win, so tie_class_hits[b][1] == ranks x problems and truth_count_sum[b] == that x N whatever
     the sharding; the multi-rank lines check it on the independently gathered sum."""
-    d = _bench(["--problems-per-step", "100", "--samples", "512", "--steps", "2", "--warmup", "1", "--resident", "2", "--dist", "2"], ranks=4)
+    d = _bench(["--problems-per-step", "100", "--samples", "512", "--steps", "2", "--warmup", "1", "--resident", "2", "--dist", "2", "--full"], ranks=4)
     assert d["exchange_check"]["closed_form"].startswith("D2: tie_class_hits[b][1] == 400") and d["allreduce_verified"] is True
-    p = _bench(["--comm", "peer", "--gpus", "4", "--share-device", "--problems-per-step", "100", "--samples", "512", "--steps", "2", "--warmup", "1",
+    p = _bench(["--comm", "peer", "--gpus", "4", "--share-device", "--full", "--problems-per-step", "100", "--samples", "512", "--steps", "2", "--warmup", "1",
                 "--resident", "2", "--dist", "5"])
     assert p["exchange_check"]["closed_form"].startswith("D5: tie_class_hits[b][1] == 0") and p["allreduce_verified"] is True
 
@@ -300,20 +329,22 @@ def test_a_wrong_sum_on_one_rank_stops_the_line(stack):
 
 # ---- round 6: one GPU ends in C3's RESULT; the N > 1 line explains its own scaling ---------------------------
 
-def test_full_pass_of_all_eight_chunks_equals_the_eight_rank_step(tmp_path):
+def test_full_pass_of_all_eight_chunks_equals_the_four_rank_step(tmp_path):
     """The timed region of the 1-GPU line cycles the chunks that fit in HBM; `c3_full` then accumulates ALL 8 chunks (problems 0 .. 8 Pc - 1,
     the sum o1.py:236-245 takes over every problem) into one buffer.  It must be, word for word (sha256 of the 8216 counters and the dump),
-    the all-reduced step of 8 ranks x Pc problems over the same global problems -- here with fewer resident slots than chunks, so that
-    several chunks are generated into freed slots -- and satisfy the closed forms of D2 / D5."""
-    shape = ["--problems-per-step", "24", "--samples", str(1 << 13), "--no-cpu-baseline"]
+    the all-reduced step of several ranks over the same global problems (RANK_PROCESSES ranks x 2 Pc problems: as many rank processes as the suite
+    may keep on one GPU at a time) -- here with fewer resident slots than chunks, so that several chunks are generated into freed slots -- and satisfy
+    the closed forms of D2 / D5."""
+    shape = ["--problems-per-step", "24", "--samples", str(1 << 13), "--no-cpu-baseline", "--full"]
     one = _bench([*shape, "--steps", "2", "--warmup", "1", "--dump", str(tmp_path / "one.npz")])
     f = one["c3_full"]
     assert f["problems"] == 192 and f["chunks"] == 8 and f["chunks_generated_after_the_timed_region"] == [3, 4, 5, 6, 7] and f["counters_words"] == 8 * 1027
-    eight = _bench([*shape[:4], "--steps", "1", "--warmup", "0", "--dump", str(tmp_path / "eight.npz")], ranks=8)
-    assert eight["c3_full"] is None and eight["counters_sha256_last_step"] == f["counters_sha256"]
+    ranks = _bench(["--problems-per-step", str(192 // RANK_PROCESSES), *shape[2:4], "--full", "--steps", "1", "--warmup", "0", "--dump", str(tmp_path / "ranks.npz")],
+                   ranks=RANK_PROCESSES)
+    assert ranks["c3_full"] is None and ranks["counters_sha256_last_step"] == f["counters_sha256"]
     full = np.load(tmp_path / "one.npz")["full"]
-    assert np.array_equal(full, np.load(tmp_path / "eight.npz")["counters"]) and full[:8 * 1025].sum() > 0
-    assert [round(a, 6) for a in f["accuracy"]] == eight["accuracy_last_step"]
+    assert np.array_equal(full, np.load(tmp_path / "ranks.npz")["counters"]) and full[:8 * 1025].sum() > 0
+    assert [round(a, 6) for a in f["accuracy"]] == ranks["accuracy_last_step"]
     # ... and one rank x 192 problems in ONE chunk
     whole = _bench(["--problems-per-step", "192", "--samples", str(1 << 13), "--no-cpu-baseline", "--steps", "1", "--warmup", "0", "--no-full-pass"])
     assert whole["c3_full"] is None and whole["counters_sha256_last_step"] == f["counters_sha256"]
@@ -325,7 +356,7 @@ def test_full_pass_of_all_eight_chunks_equals_the_eight_rank_step(tmp_path):
 
 def test_multi_rank_line_reports_kernel_balance_and_the_exposed_all_reduce():
     """A first multi-GPU run below 6x must explain itself: per-rank kernel time min / max and the exposed all-reduce are in the torch line too."""
-    d = _bench(["--problems-per-step", "64", "--samples", str(1 << 14), "--steps", "3", "--warmup", "1", "--resident", "2"], ranks=2)
+    d = _bench(["--problems-per-step", "64", "--samples", str(1 << 14), "--steps", "3", "--warmup", "1", "--resident", "2", "--full"], ranks=2)
     r = d["roofline"]
     assert 0 < r["kernel_avg_ms_per_rank_min"] <= r["kernel_avg_ms_per_rank_max"] == r["kernel_avg_ms"]
     assert r["exposed_allreduce_us"] is not None and r["exposed_allreduce_us"] > 0 and "AFTER the timed region" in r["exposed_allreduce_what"]

@@ -25,7 +25,7 @@ def newest(pattern, containing=None):
     return max(files, key=os.path.getmtime) if files else None
 
 
-lines = [f"# rocprofv3 summary {tag} (MI355X, `python bench.py --steps 8 --warmup 2 --no-cpu-baseline`; same box and session as {tag}_bench.json: tools/gpu_round.sh)", ""]
+lines = [f"# rocprofv3 summary {tag} (MI355X, `python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-live-traffic`; same box and session as {tag}_bench.json: tools/gpu_round.sh)", ""]
 ks = newest("prof_trace/*/*_kernel_stats.csv", "scv_hist_argmax")
 if ks:
     shutil.copy(ks, os.path.join(P, f"{tag}_kernel_stats.csv"))
