@@ -255,8 +255,45 @@ int scv_synth_fill_i32(scv_ctx* ctx, int32_t* answers, int32_t* tokens, int32_t*
                        uint64_t seed, int dist);
 
 /*
+ * Resampled majority vote: the EXPECTED maj@k over random orderings of one sample pool per problem (new semantics, not in the
+ * reference).  The reference's budgets T >= 2^11 vote over the FIRST N_b samples of one pool (o1.py:274-277 with the idx-keyed
+ * cache of o1.py:85-88), so each point of its curve is one draw that depends on the order the samples sit in the cache.  Here
+ * each problem's pool is shuffled R times and every budget votes over the prefixes of each ordering.
+ *   pool / tokens  int32 [P, N] (tokens may be NULL); n_valid int32 [B] (required, any order, duplicates fine); truth int32 [P]
+ * For problem p (global index pg = p_offset + p) and resample r in [r_begin, r_end):
+ *   s      = mix64((seed ^ 0xD6E8FEB86659FD93) + G * (pg + 1))                       (uint64, wrapping; mix64, G, mulhi32 as above)
+ *   perm   = [0, 1, ..., N-1];  for i in 0 .. N-2:  u = mix64(s + G * ((uint64)r * N + i + 1)),  j = i + mulhi32(hi32(u), N - i),
+ *            swap(perm[i], perm[j])                                                   (partial Fisher-Yates)
+ *   cell (p, r, b) = statistics.multimode over pool[p, perm[0 : k_b]],  k_b = clamp(n_valid[b], 0, N)
+ * A prefix of length k depends only on the first k steps (the implementation stops at max_b k_b); each is a uniformly random
+ * k-subset, and the subsets of one resample are nested across budgets, as in the reference.  Cells follow the conventions of
+ * scv_aggregate_prefix_i32: an empty subset has no hit; a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST
+ * mode, at scv_sync in DEVICE mode) or counts in bin 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m: accuracy_from_tie_classes(tie[b], P * R)
+ *                        (o1_inference_scaling_laws_amd/scoring.py) is the expected maj@k_b, exact_accuracy_... its exact rational
+ *   token_sum_out        int64 [B]        (NULL ok; requires tokens) tokens of the votes in the subsets
+ *   truth_count_sum_out  int64 [B]        (NULL ok) votes equal to the truth in the subsets
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) the same class counts per resample, summed over problems only
+ *                        (m < M): the spread of the curve across orderings -- the reference's curve is one such draw.  A hit with
+ *                        n_modes >= M sets error bit 1 (SCV_ERR_ARG at scv_sync, as in scv_bootstrap); nothing is dropped silently.
+ * DEVICE mode ACCUMULATES into every output (+=) and only enqueues: no allocation, no synchronisation, legal under hipGraph capture.
+ * HOST mode overwrites and blocks.  Slices of r and shards of p (p_offset) add up to the whole call bit for bit, so chunked and
+ * multi-GPU use needs nothing more.  Limits: 1 <= N <= 256, 1 <= B <= 32, 0 <= r_begin <= r_end < 2^31, p_offset >= 0, M >= 1 when
+ * per_resample_out is given; anything else is SCV_ERR_ARG.  One lane per (problem, resample), P * R * max_b k_b shuffle steps:
+ * VALU / LDS-bound, the pool is read once (csrc/scvote_resample.hip.h).  Stat "resample_calls" counts the launches.
+ */
+int scv_resample_prefix_i32(scv_ctx* ctx,
+                            const int32_t* pool, const int32_t* tokens,
+                            const int32_t* n_valid, const int32_t* truth,
+                            int64_t P, int32_t B, int64_t N, int64_t p_offset,
+                            int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                            int64_t* tie_class_hits_out, int64_t* token_sum_out,
+                            int64_t* truth_count_sum_out, int64_t* per_resample_out);
+
+/*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit had n_modes >= M; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the
@@ -352,7 +389,7 @@ int scv_host_free(void* p);
  * sort per problem -- queued, that is: a DEVICE-mode launch may find budgets it does not serve and leave them to the kernel behind it), "prefix_tokens" (launches of
  * scv_sort_prefix2<true>: the token sums of pools of 68 .. 128 votes out of token steps of the sort kernel's launch), "host_small_calls" / "host_pipelined_calls" (HOST-mode calls served by the one-block small path / by
  * the staging pipeline), "host_thread_start_failures" (worker threads of the staging pipeline the system refused to start: the
- * pipeline runs with the threads it has, the calling thread at least). */
+ * pipeline runs with the threads it has, the calling thread at least), "resample_calls" (launches of scv_resample_prefix_i32). */
 int scv_get_stat(scv_ctx* ctx, const char* key, int64_t* out);
 
 int scv_device_count(void);

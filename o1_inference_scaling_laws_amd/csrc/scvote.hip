@@ -179,6 +179,7 @@ struct scv_ctx {
     size_t small_bytes = 0;
     int small_call_kb = 1024;       // option "host_small_kb": calls whose inputs + outputs fit in this many KiB take the small path (0: never)
     int64_t stat_small_calls = 0, stat_pipelined_calls = 0;
+    int64_t stat_resample_calls = 0;    // scv_resample_prefix_i32 calls that launched the kernel
 };
 
 namespace {
@@ -211,6 +212,7 @@ using scv::pick_dense_kernel;
 using scv::pick_sort_kernel;
 using scv::pick_prefix_pool_kernel;
 using scv::pick_sort_prefix_kernel;
+using scv::pick_resample_kernel;
 
 // Every entry point runs on the ctx device and leaves the caller's current HIP device as it found it
 // (a process driving several GPUs from one thread -- MultiDeviceEngine -- must not have torch's
@@ -1062,7 +1064,7 @@ int check_err_word(scv_ctx* ctx, uint32_t w) {
     }
     if ((w & 1u) && !(ctx->flags & SCV_FLAG_CLAMP_TO_INVALID_BIN))
         return fail(SCV_ERR_DOMAIN, "a vote outside bins 0..1023 was seen; results are invalid");
-    if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap: a drawn hit had n_modes >= M");
+    if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap / resample: a hit had n_modes >= M");
     if (w & 8u) return fail(SCV_ERR_ARG, "prefix_path = 5 promised budgets that are 0, a power of two or >= N: the list in n_valid is not; nothing was computed");
     return SCV_OK;
 }
@@ -1518,6 +1520,131 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
                           tie_class_hits_out, token_sum_out, truth_count_sum_out);
 }
 
+
+// scv_resample_prefix_i32 on device pointers: one launch of scv_resample_prefix<tok> (scvote_resample.hip.h), accumulating into the outputs.
+// Workgroups of 256 / 128 / 64 lanes: the one that keeps the most waves resident per CU (LDS: 2 * 4 * ceil(N / 4) bytes per lane + the
+// problem rows a chunk touches + the per-budget tables), the larger on a tie (fewer tables to flush).  Persistent grid.
+int launch_resample(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
+                    int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                    int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    if (P == 0 || R == 0) return SCV_OK;
+    const bool tok = tokens != nullptr;
+    const scv::ResampleFn fn = pick_resample_kernel(tok);
+    SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+    int best_lanes = 0, best_np = 0, best_per_cu = 0;
+    size_t best_lds = 0;
+    for (int lanes = scv::kResampleMaxLanes; lanes >= 64; lanes >>= 1) {
+        const int64_t np = std::min<int64_t>(P, (lanes - 1) / R + 2);
+        const size_t lds = (size_t)scv::resample_lds_words((int)N, B, lanes, (int)np) * sizeof(uint32_t);
+        if ((int64_t)lds > ctx->lds_max) continue;
+        int per_cu = 0;
+        SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds));
+        if (per_cu < 1) continue;
+        if (per_cu * lanes > best_per_cu * best_lanes) { best_lanes = lanes; best_np = (int)np; best_per_cu = per_cu; best_lds = lds; }
+    }
+    if (!best_lanes) return fail(SCV_ERR_ARG, "resample: N=%lld B=%d does not fit the LDS of one workgroup", (long long)N, B);
+    scv::ResampleArgs a;
+    a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
+    a.P = P; a.p_offset = p_offset; a.seed = seed;
+    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M; a.np_max = best_np;
+    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
+    a.token_sum = tok ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
+    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
+    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
+    a.err_flag = err;
+    const int64_t nchunks = (P * R + best_lanes - 1) / best_lanes;
+    int64_t grid = (int64_t)ctx->num_cus * best_per_cu;
+    if (grid > nchunks) grid = nchunks;
+    if (ctx->grid_override > 0) grid = ctx->grid_override;
+    EventPair* ev = nullptr;
+    if (int rc = next_event_pair(ctx, &ev)) return rc;
+    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)best_lanes), best_lds, ctx->stream, a);
+    SCV_HIP(hipGetLastError());
+    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
+    ctx->stat_resample_calls += 1;
+    ctx->err_dirty = true;
+    return SCV_OK;
+}
+
+// HOST mode: inputs and zeroed outputs in one device block behind one upload, the kernel, one download, one stream sync.  Calls that fit
+// "host_small_kb" go through the context's pinned block (the reference's own sizes); larger ones copy the caller's memory directly.
+// The kernel reports into the block's own error word.
+int resample_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
+                  int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                  int64_t* tie_out, int64_t* tok_out, int64_t* tcs_out, int64_t* per_out) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    const size_t pool_bytes = (size_t)P * N * sizeof(int32_t);
+    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
+    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
+    size_t off = 0;
+    const size_t o_pool = off; off = align_up(off + pool_bytes, 256);
+    const size_t o_tok = off; off = align_up(off + (tokens ? pool_bytes : 0), 256);
+    const size_t o_truth = off; off = align_up(off + (size_t)P * sizeof(int32_t), 256);
+    const size_t o_nv = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
+    const size_t o_out = off;                                                        // tie | token sums | truth sums | per_resample | error word
+    const size_t o_ts = o_out + tie_bytes, o_tc = o_ts + sums_bytes, o_per = o_tc + sums_bytes;
+    const size_t o_err = align_up(o_per + per_bytes, 256);
+    const size_t total = o_err + 256;
+    const bool small = ctx->small_call_kb > 0 && total <= ((size_t)ctx->small_call_kb << 10);
+    hipStream_t s = ctx->stream;
+    char* db = nullptr;
+    char* hb = nullptr;
+    if (small) {
+        if (total > ctx->small_bytes) {
+            const size_t want = (size_t)ctx->small_call_kb << 10;
+            if (ctx->small_h) { SCV_HIP(hipHostFree(ctx->small_h)); ctx->small_h = nullptr; }
+            if (ctx->small_d) { SCV_HIP(hipFree(ctx->small_d)); ctx->small_d = nullptr; }
+            ctx->small_bytes = 0;
+            SCV_HIP(hipHostMalloc(&ctx->small_h, want, hipHostMallocDefault));
+            SCV_HIP(hipMalloc(&ctx->small_d, want));
+            ctx->small_bytes = want;
+        }
+        hb = static_cast<char*>(ctx->small_h);
+        db = static_cast<char*>(ctx->small_d);
+        memcpy(hb + o_pool, pool, pool_bytes);
+        if (tokens) memcpy(hb + o_tok, tokens, pool_bytes);
+        memcpy(hb + o_truth, truth, (size_t)P * sizeof(int32_t));
+        memcpy(hb + o_nv, n_valid, (size_t)B * sizeof(int32_t));
+        memset(hb + o_out, 0, total - o_out);
+        SCV_HIP(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, s));
+    } else {
+        if (int rc = ensure_stage(ctx, total)) return rc;
+        db = static_cast<char*>(ctx->d_stage);
+        SCV_HIP(hipMemcpyAsync(db + o_pool, pool, pool_bytes, hipMemcpyHostToDevice, s));
+        if (tokens) SCV_HIP(hipMemcpyAsync(db + o_tok, tokens, pool_bytes, hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemcpyAsync(db + o_truth, truth, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemcpyAsync(db + o_nv, n_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
+    }
+    if (int rc = launch_resample(ctx, reinterpret_cast<const int32_t*>(db + o_pool), tokens ? reinterpret_cast<const int32_t*>(db + o_tok) : nullptr,
+                                 reinterpret_cast<const int32_t*>(db + o_nv), reinterpret_cast<const int32_t*>(db + o_truth), P, B, N, p_offset,
+                                 r_begin, r_end, seed, M, reinterpret_cast<int64_t*>(db + o_out), reinterpret_cast<int64_t*>(db + o_ts),
+                                 reinterpret_cast<int64_t*>(db + o_tc), per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
+                                 reinterpret_cast<uint32_t*>(db + o_err))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    uint32_t w = 0;
+    if (small) {
+        SCV_HIP(hipMemcpyAsync(hb + o_out, db + o_out, total - o_out, hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipStreamSynchronize(s));
+        memcpy(tie_out, hb + o_out, tie_bytes);
+        if (tok_out) memcpy(tok_out, hb + o_ts, sums_bytes);
+        if (tcs_out) memcpy(tcs_out, hb + o_tc, sums_bytes);
+        if (per_out) memcpy(per_out, hb + o_per, per_bytes);
+        memcpy(&w, hb + o_err, sizeof w);
+    } else {
+        SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
+        if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
+        if (tcs_out) SCV_HIP(hipMemcpyAsync(tcs_out, db + o_tc, sums_bytes, hipMemcpyDeviceToHost, s));
+        if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipStreamSynchronize(s));
+    }
+    return check_err_word(ctx, w);
+}
 }  // namespace
 
 extern "C" {
@@ -1610,6 +1737,37 @@ int scv_aggregate_bootstrap_i32(scv_ctx* ctx, const int32_t* answers, const int3
         // shape or occupancy did not allow the fused form: the bootstrap is queued behind the vote on the same stream
         ctx->stat_boot_separate += 1;
         return scv_bootstrap(ctx, cells_out, P, B, r_begin, r_end, seed, M, SCV_MEM_DEVICE, counts_out);
+    });
+}
+
+int scv_resample_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
+                            int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                            int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* truth_count_sum_out,
+                            int64_t* per_resample_out) {
+    return guarded([&]() -> int {
+        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
+        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
+            return fail(SCV_ERR_ARG, "resample: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
+                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
+        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "resample: P * (r_end - r_begin) exceeds 2^62");
+        if (!n_valid || !tie_class_hits_out) return fail(SCV_ERR_ARG, "resample: n_valid and tie_class_hits_out are required");
+        if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "resample: pool and truth are required");
+        if (token_sum_out && !tokens) return fail(SCV_ERR_ARG, "resample: token_sum_out needs tokens");
+        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "resample: per_resample_out needs M >= 1 (got %d)", M);
+        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_resample(ctx, pool, tokens, n_valid, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out,
+                                   token_sum_out, truth_count_sum_out, per_resample_out, ctx->d_err);
+        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing drawn, all zero
+            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
+            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
+            return SCV_OK;
+        }
+        return resample_host(ctx, pool, tokens, n_valid, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out,
+                             token_sum_out, truth_count_sum_out, per_resample_out);
     });
 }
 
@@ -1716,6 +1874,7 @@ int scv_get_stat(scv_ctx* ctx, const char* key, int64_t* out) {
         else if (!strcmp(key, "few_votes")) *out = ctx->stat_few_votes;
         else if (!strcmp(key, "host_small_calls")) *out = ctx->stat_small_calls;
         else if (!strcmp(key, "host_pipelined_calls")) *out = ctx->stat_pipelined_calls;
+        else if (!strcmp(key, "resample_calls")) *out = ctx->stat_resample_calls;
         else if (!strcmp(key, "host_thread_start_failures")) *out = ctx->pipe ? ctx->pipe->pool.start_failures : 0;
         else return fail(SCV_ERR_ARG, "unknown stat '%s'", key);
         return SCV_OK;

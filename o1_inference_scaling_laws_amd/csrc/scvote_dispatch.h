@@ -68,6 +68,25 @@ constexpr int sort_prefix_classes(int nv) { int l = 0; while ((1 << l) < nv / 2)
 constexpr long long sort_prefix_tail_words(int nv, int B) { return 16 + ((B + 3) & ~3) + ((sort_prefix_classes(nv) * (nv + 1) + 1) & ~1) + 4 * sort_prefix_classes(nv); }
 RegKernel pick_sort_prefix_kernel(int nv, bool tok);
 
+// scv_resample_prefix<tok>: expected majority vote over random orderings of one pool per problem (scv_resample_prefix_i32,
+// scvote_resample.hip.h).  One lane per (problem, resample), lanes problem-major, a power-of-two workgroup of 64 / 128 / 256 lanes.
+struct ResampleArgs {
+    const int32_t* pool; const int32_t* tokens; const int32_t* n_valid; const int32_t* truth;
+    int64_t P; int64_t p_offset; uint64_t seed;
+    int32_t N, B, R, r_begin, M, np_max;                 // np_max: problem rows a workgroup's chunk of lanes can touch
+    unsigned long long* tie_hits; unsigned long long* token_sum; unsigned long long* truth_sum; unsigned long long* per_resample;
+    uint32_t* err_flag;
+};
+using ResampleFn = void (*)(const ResampleArgs);
+constexpr int kResampleMaxN = 256, kResampleMaxB = 32, kResampleMaxLanes = 256;
+// LDS words of a workgroup of `lanes` lanes (the kernel's layout, in this order): per-budget sums (2 B int64) | tie classes [B][N + 1] |
+// sorted budgets and their order (2 x 32) | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
+// the rows as byte codes [np_max][N4] | the lanes' Fisher-Yates arrays [N4][lanes] | their counts [N4][lanes]
+constexpr long long resample_lds_words(int N, int B, int lanes, int np_max) {
+    return 4LL * B + (long long)B * (N + 1) + 64 + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) + 2LL * lanes * ((N + 3) / 4);
+}
+ResampleFn pick_resample_kernel(bool tok);
+
 // ---- shared by the table translation units ------------------------------------------------------------------------
 template <int RL2, int T, int U>
 inline KernelFn stream_tok(bool tok, bool xtra) {

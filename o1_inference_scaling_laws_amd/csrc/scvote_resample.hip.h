@@ -1,0 +1,218 @@
+// scvote_resample.hip.h -- expected majority vote over random orderings of one sample pool per problem (scv_resample_prefix<TOK>).
+//
+// The reference's budgets T >= 2^11 vote over the FIRST N_b samples of one pool (o1.py:274-277 with the idx-keyed cache of
+// o1.py:85-88): every point of that curve is one draw.  scv_resample_prefix_i32 (include/scvote.h) draws R orderings per problem
+// by a counter-based partial Fisher-Yates shuffle and votes over the prefixes of each: sum over orderings of the tie-class hits is
+// P * R times the expected maj@k.  The work is P * R * max_b k_b shuffle steps over a pool read once: VALU / LDS-bound, not HBM-bound.
+//
+// How:
+//  * one lane per (problem, resample), flattened problem-major, so a wave touches one or two problems when R >= 64.  A persistent
+//    workgroup walks chunks of `lanes` consecutive (problem, resample) pairs.
+//  * per chunk, every problem row the chunk touches is re-encoded ONCE into LDS by one wave: a 1024-bit presence map of the votes
+//    (votes outside 0..1023 go to bin 1023 and raise error bit 0), its running popcount, and from them every vote's rank among the
+//    row's distinct values -- a dense code < N (<= 256, one byte) -- and the truth's code, or -1 when the truth is not in the row or
+//    not in the bins (it never hits).
+//  * every lane owns two byte arrays of ceil(N / 4) words in LDS, laid out [slot / 4][lane]: the Fisher-Yates array and the counts over
+//    the row's codes.  Byte e of lane l lives in word (e / 4) * lanes + l, so the 32 lanes of an access group always hit 32 different
+//    banks, whatever slot each lane picked.  Without tokens the shuffled array holds the CODES themselves (one LDS read less per
+//    step); with tokens it holds pool indices (0..255), the code is looked up in the row and the token read from global memory (the
+//    row is a few hundred bytes that every lane of the problem reads: L1 / L2 hits).
+//  * step i: u = mix64(arg), arg += G; j = i + mulhi32(hi32(u), N - i); x = a[j]; a[j] = a[i] (slot i is never read again);
+//    c = ++cnt[code].  Counts only grow by one, so the mode statistics are kept running: c > max -> (max, n_modes) = (c, 1);
+//    c == max -> n_modes + 1.  Byte counts are exact: a count of 256 needs 256 votes of one value -- only at the very last step of
+//    N = 256, and that count is never read back.  The truth's count is a register (tc += code == truth code): hit = tc == max > 0.
+//  * budgets are sorted once per workgroup (rank sort in LDS) and are the same for every lane, so the boundary test is uniform; at
+//    a boundary the wave adds its lanes' hits to the workgroup's LDS tables (one ballot for the common n_modes == 1, an LDS atomic
+//    for the rest), its truth-count and token sums (DPP reductions), and -- when requested -- each hit to per_resample with one
+//    global atomic (lanes of a wave hold different resamples).  The tables are flushed with non-returning int64 atomics once per
+//    workgroup.  No scratch buffer, no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
+//
+// LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
+#pragma once
+
+#include "scvote_kernels.hip.h"
+#include "scvote_dispatch.h"
+
+namespace scv {
+
+constexpr uint64_t kResampleSalt = 0xD6E8FEB86659FD93ull;
+
+// byte e of a lane's [slot / 4][lane] array: word (e >> 2) * lanes + lane
+__device__ __forceinline__ uint32_t resample_byte(uint32_t e, int lanes_log2, uint32_t lane_byte) {
+    return ((e >> 2) << (lanes_log2 + 2)) + (e & 3u) + lane_byte;
+}
+
+// one wave re-encodes the pool row of problem p into value-ordered byte codes: row_codes (bytes), meta[0] = the truth's code or -1,
+// meta[1] = the number of distinct values.  scr: 64 words of the wave's own.  Returns true when a vote was outside 0..1023.
+__device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64_t p, uint8_t* row_codes, int32_t* meta, uint32_t* scr, int lane) {
+    const int N = a.N;
+    const int32_t* row = a.pool + p * (int64_t)N;
+    if (lane < 32) scr[lane] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int32_t v[kResampleMaxN / 64];
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < kResampleMaxN / 64; ++k) {
+        const int e = lane + 64 * k;
+        int32_t x = e < N ? row[e] : 0;
+        if ((uint32_t)x >= (uint32_t)kBins) { bad = bad || e < N; x = kBins - 1; }
+        v[k] = x;
+        if (e < N) atomicOr(&scr[x >> 5], 1u << (x & 31));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // exclusive popcount prefix of the 32 map words (lanes 0..31), total in lane 31's inclusive value
+    const uint32_t word = lane < 32 ? scr[lane] : 0u;
+    uint32_t incl = (uint32_t)__popc(word);
+#pragma unroll
+    for (int d = 1; d < 32; d <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, d, 64);
+        if ((lane & 31) >= d) incl += t;
+    }
+    if (lane < 32) scr[32 + lane] = incl - (uint32_t)__popc(word);
+    const int32_t distinct = __shfl((int)incl, 31, 64);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int k = 0; k < kResampleMaxN / 64; ++k) {
+        const int e = lane + 64 * k;
+        if (e < N) {
+            const uint32_t x = (uint32_t)v[k];
+            row_codes[e] = (uint8_t)(scr[32 + (x >> 5)] + (uint32_t)__popc(scr[x >> 5] & ((1u << (x & 31)) - 1u)));
+        }
+    }
+    if (lane == 0) {
+        const int32_t t = a.truth[p];
+        int32_t tcode = -1;
+        if ((uint32_t)t < (uint32_t)kBins && ((scr[t >> 5] >> (t & 31)) & 1u))
+            tcode = (int32_t)(scr[32 + (t >> 5)] + (uint32_t)__popc(scr[t >> 5] & ((1u << (t & 31)) - 1u)));
+        meta[0] = tcode;
+        meta[1] = distinct;
+    }
+    return bad;
+}
+
+template <bool TOK>
+__global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const ResampleArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem_wg[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lanes = (int)blockDim.x, nwaves = lanes >> 6;
+    const int lanes_log2 = 31 - __clz(lanes);
+    const int N = a.N, B = a.B, N4 = (N + 3) >> 2, TC = N + 1;
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(smem_wg);      // [B] truth-count sums | [B] token sums
+    uint32_t* tie = smem_wg + 4 * B;                                                // [B][N + 1]
+    int32_t* ks = reinterpret_cast<int32_t*>(tie + B * TC);                         // [32] budgets, ascending
+    int32_t* ord = ks + 32;                                                         // [32] their indices
+    uint32_t* scr = reinterpret_cast<uint32_t*>(ord + 32);                          // [nwaves][64]
+    int32_t* meta = reinterpret_cast<int32_t*>(scr + 64 * nwaves);                  // [np_max][2]
+    uint32_t* rows = reinterpret_cast<uint32_t*>(meta + 2 * a.np_max);              // [np_max][N4]
+    uint32_t* arr = rows + a.np_max * N4;                                           // [N4][lanes]
+    uint32_t* cnt = arr + N4 * lanes;                                               // [N4][lanes]
+    uint8_t* arr_b = reinterpret_cast<uint8_t*>(arr);
+    uint8_t* cnt_b = reinterpret_cast<uint8_t*>(cnt);
+    const uint8_t* rows_b = reinterpret_cast<const uint8_t*>(rows);
+
+    for (int i = tid; i < B * TC; i += lanes) tie[i] = 0u;
+    if (tid < 2 * B) acc[tid] = 0ull;
+    if (tid < B) {                                                                  // rank sort: ties keep index order
+        int32_t k = a.n_valid[tid];
+        k = k < 0 ? 0 : (k > N ? N : k);
+        int rank = 0;
+        for (int b = 0; b < B; ++b) {
+            int32_t kb = a.n_valid[b];
+            kb = kb < 0 ? 0 : (kb > N ? N : kb);
+            rank += (kb < k || (kb == k && b < tid)) ? 1 : 0;
+        }
+        ks[rank] = k;
+        ord[rank] = tid;
+    }
+    __syncthreads();
+    const int32_t kmax = ks[B - 1];
+    int q0 = 0;
+    while (q0 < B && ks[q0] == 0) ++q0;                                              // empty subsets: no hit, nothing to add
+    const int64_t R = a.R, total = a.P * R;
+    const int64_t nchunks = (total + lanes - 1) / lanes;
+    const uint32_t lane_byte = (uint32_t)tid << 2;
+    bool bad = false, overflow = false;
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int64_t t0 = chunk * lanes;
+        const int64_t p_lo = t0 / R;
+        int64_t p_hi = (t0 + lanes - 1) / R;
+        if (p_hi > a.P - 1) p_hi = a.P - 1;
+        for (int64_t pl = wave; pl <= p_hi - p_lo; pl += nwaves)
+            bad |= resample_encode_row(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
+        __syncthreads();
+        const int64_t t = t0 + tid;
+        const bool live = t < total;
+        const int64_t p = (live ? t : total - 1) / R;
+        const int32_t rr = (int32_t)((live ? t : total - 1) - p * R);
+        const int32_t row = (int32_t)(p - p_lo);
+        const int32_t tcode = meta[2 * row], distinct = meta[2 * row + 1];
+        for (int w = 0; w < N4; ++w) arr[(w << lanes_log2) + tid] = TOK ? 0x03020100u + 0x04040404u * (uint32_t)w : rows[row * N4 + w];
+        for (int w = 0; w < ((distinct + 3) >> 2); ++w) cnt[(w << lanes_log2) + tid] = 0u;
+        const uint8_t* my_row = rows_b + (int64_t)row * N4 * 4;
+        const int32_t* tok_row = TOK ? a.tokens + p * (int64_t)N : nullptr;
+        const uint64_t s = mix64((a.seed ^ kResampleSalt) + kGolden * (uint64_t)(a.p_offset + p + 1));
+        uint64_t arg = s + kGolden * ((uint64_t)(uint32_t)(a.r_begin + rr) * (uint64_t)N + 1ull);
+        uint32_t maxc = 0, nmodes = 0, tc = 0;
+        long long tok = 0;
+        int q = q0;
+        int32_t next_k = q < B ? ks[q] : 0x7fffffff;
+        for (int32_t i = 0; i < kmax; ++i) {
+            const uint64_t u = mix64(arg);
+            arg += kGolden;
+            const uint32_t j = (uint32_t)i + mulhi32((uint32_t)(u >> 32), (uint32_t)(N - i));
+            const uint32_t ai = arr_b[resample_byte((uint32_t)i, lanes_log2, lane_byte)];
+            const uint32_t aj = resample_byte(j, lanes_log2, lane_byte);
+            const uint32_t x = arr_b[aj];
+            arr_b[aj] = (uint8_t)ai;
+            const uint32_t code = TOK ? (uint32_t)my_row[x] : x;
+            const uint32_t ac = resample_byte(code, lanes_log2, lane_byte);
+            const uint32_t c = (uint32_t)cnt_b[ac] + 1u;
+            cnt_b[ac] = (uint8_t)c;
+            if (c > maxc) { maxc = c; nmodes = 1u; }
+            else if (c == maxc) nmodes += 1u;
+            tc += (int32_t)code == tcode ? 1u : 0u;
+            if (TOK) tok += tok_row[x];
+            if (i + 1 == next_k) {
+                const bool hit = live && tcode >= 0 && tc == maxc;
+                const uint32_t tcs = wave_sum_u32(live ? tc : 0u);
+                const long long toks = TOK ? wave_sum_i64(live ? tok : 0ll) : 0ll;
+                const unsigned long long ones = __ballot(hit && nmodes == 1u);
+                do {                                                                  // every budget of this size
+                    const int32_t b = ord[q];
+                    if (lane == 0) {
+                        if (ones) atomicAdd(&tie[b * TC + 1], (uint32_t)__popcll(ones));
+                        if (tcs) atomicAdd(&acc[b], (unsigned long long)tcs);
+                        if (TOK && toks) atomicAdd(&acc[B + b], (unsigned long long)toks);
+                    }
+                    if (hit && nmodes != 1u) atomicAdd(&tie[b * TC + nmodes], 1u);
+                    if (hit && a.per_resample) {
+                        if (nmodes < (uint32_t)a.M) atomicAdd(&a.per_resample[((int64_t)rr * B + b) * a.M + nmodes], 1ull);
+                        else overflow = true;
+                    }
+                    ++q;
+                    next_k = q < B ? ks[q] : 0x7fffffff;
+                } while (next_k == i + 1);
+            }
+        }
+        __syncthreads();                                                              // the rows are rewritten by the next chunk
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(a.err_flag, 1u);
+    if (__ballot(overflow) && lane == 0) atomicOr(a.err_flag, 2u);
+    __syncthreads();
+    for (int i = tid; i < B * TC; i += lanes) {
+        const uint32_t v = tie[i];
+        if (v) atomicAdd(&a.tie_hits[(int64_t)(i / TC) * SCV_TIE_CLASSES + (i % TC)], (unsigned long long)v);
+    }
+    if (tid < B) {
+        if (a.truth_sum && acc[tid]) atomicAdd(&a.truth_sum[tid], acc[tid]);
+        if (TOK && a.token_sum && acc[B + tid]) atomicAdd(&a.token_sum[tid], acc[B + tid]);
+    }
+}
+
+}  // namespace scv

@@ -1,0 +1,41 @@
+"""Accuracy-vs-token-budget curves from resampled majority votes (Engine.resample_prefix, include/scvote.h
+scv_resample_prefix_i32).
+
+The reference's majority-vote tail (o1.py:266-277: T >= 2^11 votes over the first N = T // 2^11 samples of the 2^11-token pool)
+is one ordering of the cache.  ``expected_majority_records`` averages each point over ``resamples`` random orderings of the same
+pool and returns it in the reference's log schema, so plot_helpers can draw the smoothed tail next to the single-ordering one."""
+from __future__ import annotations
+
+import numpy as np
+
+from .o1_dropin import majority_vote_budgets
+
+KEY_LIMIT = 2 ** 11          # o1.py:274: actual_token_limit = min(2 ** 11, token_limit)
+
+
+def resampled_budgets(token_limits=None, shade_regions: bool = False):
+    """[(token_limit, N)] of the budgets that vote over prefixes of the 2^11-token pool (o1_dropin.majority_vote_budgets)."""
+    if token_limits is None:
+        return [(t, n) for t, key, n in majority_vote_budgets(shade_regions) if key == KEY_LIMIT]
+    out = []
+    for t in token_limits:
+        t = int(t)
+        if t < KEY_LIMIT:
+            raise ValueError(f"token_limit {t} < 2^11 votes over one sample of its own pool, not over a prefix of the 2^11-token pool")
+        out.append((t, t // KEY_LIMIT))
+    return out
+
+
+def expected_majority_records(engine, pool, truth, tokens, token_limits, resamples: int, seed: int):
+    """pool / tokens int32 [P, Npool] (the 2^11-token samples of each problem, in cache order), truth int32 [P].  For every
+    token limit T >= 2^11: the expected accuracy of the majority vote over N = T // 2^11 samples drawn without replacement
+    (average over ``resamples`` orderings) and the expected tokens used, as records
+    {'token_limit', 'accuracy', 'avg_tokens_used'} (o1.py:278-283).  ``tokens`` may be None (avg_tokens_used is then 0.0)."""
+    budgets = resampled_budgets(token_limits)
+    pool = np.asarray(pool, dtype=np.int32)
+    ns = np.array([n for _t, n in budgets], dtype=np.int32)
+    if len(ns) and ns.max() > pool.shape[1]:
+        raise ValueError(f"token limit {budgets[int(ns.argmax())][0]} needs {int(ns.max())} samples per problem; the pool has {pool.shape[1]}")
+    res = engine.resample_prefix(pool, truth, ns, resamples, seed, tokens=tokens, M=0)
+    return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
+            for b, (t, _n) in enumerate(budgets)]

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import TIE_CLASSES, check
+from .resample import ResampleResult
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
 CELL_DTYPE = np.dtype(
@@ -257,6 +258,38 @@ class Engine:
         check(self._L.scv_bootstrap(self._ctx, _np_ptr(cells), P, B, r_begin, r_end, seed, M, _lib.MEM_HOST, _np_ptr(out)))
         return out
 
+
+    def resample_prefix(self, pool, truth, n_valid, resamples: int, seed: int, tokens=None, r_begin: int = 0, p_offset: int = 0,
+                        M: int | None = None) -> ResampleResult:
+        """Expected majority vote over ``resamples`` random orderings of each pool (scv_resample_prefix_i32; CPU mirror:
+        resample.py).  pool int32 [P, N] (numpy, N <= 256), n_valid int32 [B] (B <= 32): budget b votes over the first n_valid[b]
+        votes of each ordering r in [r_begin, r_begin + resamples).  Every denominator of the result is P * resamples.
+        ``M``: classes of ``per_resample`` (None: max budget + 1, which no hit can exceed; 0: per_resample is not computed).  Blocking."""
+        pool = np.ascontiguousarray(pool, dtype=np.int32)
+        if pool.ndim != 2:
+            raise ValueError("pool must be [P, N]")
+        P, N = pool.shape
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
+        if truth.shape != (P,) or n_valid.ndim != 1:
+            raise ValueError("truth must be [P] and n_valid [B]")
+        B = n_valid.shape[0]
+        if tokens is not None:
+            tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+            if tokens.shape != pool.shape:
+                raise ValueError("tokens must match pool")
+        R = int(resamples)
+        if M is None:
+            M = int(np.clip(n_valid, 0, N).max(initial=0)) + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64)
+        tcs = np.zeros((B,), dtype=np.int64)
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        check(self._L.scv_resample_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth), P, B, N, p_offset,
+                                              r_begin, r_begin + R, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
+                                              _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
+        return ResampleResult(P, R, tie, tok, tcs, per)
+
     # ---- DEVICE mode (torch tensors; asynchronous on torch's current stream) --------------------
 
     def _device_call(self, votes, votes_name, row_shape, truth, tokens, n_valid, counters, cells, cell_tokens, overwrite, want_no_cells=True):
@@ -380,6 +413,46 @@ class Engine:
         check(self._L.scv_bootstrap(self._ctx, C.c_void_p(cells.data_ptr()), P, B, r_begin, r_end, seed, M,
                                     _lib.MEM_DEVICE, C.c_void_p(out.data_ptr())))
         return out
+
+    def resample_prefix_device(self, pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
+                               tie_class_hits=None, token_sum=None, truth_count_sum=None, per_resample=None, M: int | None = None):
+        """DEVICE-mode resample_prefix: pool / tokens torch.int32 cuda [P, N], n_valid [B], truth [P].  ACCUMULATES into the given
+        int64 buffers (tie_class_hits [B, 1025], token_sum [B], truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left
+        None are allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise
+        (a hit with n_modes >= M is reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
+        import torch
+        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
+            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
+        self._check_device(pool, "pool")
+        P, N = int(pool.shape[0]), int(pool.shape[1])
+        dev = pool.device
+        B = int(n_valid.shape[0])
+        for name, t, shape in (("truth", truth, (P,)), ("tokens", tokens, (P, N)), ("n_valid", n_valid, (B,))):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
+        R = int(r_end) - int(r_begin)
+
+        def buf(t, shape, name):
+            if t is None:
+                return torch.zeros(shape, dtype=torch.int64, device=dev)
+            if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA int64 tensor {tuple(shape)} on {dev}")
+            return t
+        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
+        token_sum = buf(token_sum, (B,), "token_sum") if tokens is not None else None
+        truth_count_sum = buf(truth_count_sum, (B,), "truth_count_sum")
+        if per_resample is not None and M is None:
+            M = int(per_resample.shape[2])
+        if M is not None:
+            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        self.use_torch_stream()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self._L.scv_resample_prefix_i32(self._ctx, ptr(pool), ptr(tokens), ptr(n_valid), ptr(truth), P, B, N, p_offset, r_begin, r_end,
+                                              seed, M if M is not None else 1, _lib.MEM_DEVICE, ptr(tie_class_hits), ptr(token_sum),
+                                              ptr(truth_count_sum), ptr(per_resample)))
+        return tie_class_hits, token_sum, truth_count_sum, per_resample
 
 
 class MultiDeviceEngine:
