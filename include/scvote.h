@@ -292,6 +292,33 @@ int scv_resample_prefix_i32(scv_ctx* ctx,
                             int64_t* truth_count_sum_out, int64_t* per_resample_out);
 
 /*
+ * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
+ * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
+ * seed and nothing left to converge.
+ *   pool int32 [P, N]; n_valid int32 [B] (required, any order, duplicates fine); truth int32 [P]
+ * Per problem p with budgets k_b = clamp(n_valid[b], 0, N), c_v the votes of value v in pool[p, 0:N] and c_t those of the truth (0 when
+ * absent):
+ *   E_k = C(N,k)^-1 sum_{j=1..min(c_t,k)} C(c_t,j) sum_u A_j(k-j,u) / (1+u)    the expected score (o1.py:202-213: 1 / n_modes on a hit)
+ *   H_k = C(N,k)^-1 sum_{j=1..min(c_t,k)} C(c_t,j) sum_u A_j(k-j,u)            the probability that the truth is among the modes
+ *   A_j(s,u) = [x^s y^u] prod_{v != t} ( sum_{i=0..min(c_v, j-1)} C(c_v,i) x^i + [c_v >= j] C(c_v,j) x^j y )
+ * (j truth votes in the subset; every other value at most j votes, u of them tied at exactly j).  Cells follow scv_resample_prefix_i32:
+ * a vote outside 0..1023 counts as value 1023 and sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at scv_sync in DEVICE mode;
+ * no error under SCV_FLAG_CLAMP_TO_INVALID_BIN); a truth outside the bins never hits; k = 0 scores 0.
+ *   expected_score_out  float64 [P, B] (required)  E_k_b;  mean over p is the expected maj@k_b (curves.exact_majority_records)
+ *   hit_prob_out        float64 [P, B] (NULL ok)   H_k_b
+ * Computed in float64 with no subtraction anywhere (sum_u A / (1+u) = integral_0^1 A(s,y) dy by an exact Gauss-Legendre rule;
+ * csrc/scvote_expected.hip.h): every output is within 1e-12 relative of the exact rational, and exactly 0.0 when that is 0.  Each (p, b)
+ * is summed in one fixed order: repeated calls, HOST and DEVICE mode, and shards of p (pool + p0 * N, truth + p0, out + p0 * B) give the
+ * same bits.  Outputs are OVERWRITTEN in both modes.  DEVICE mode only enqueues: no allocation, no synchronisation, legal under hipGraph
+ * capture.  HOST mode stages chunks of problems through device memory and blocks.  Limits: 1 <= N <= 256, 1 <= B <= 32, P >= 0 (P = 0 does
+ * nothing); anything else is SCV_ERR_ARG.  One workgroup per problem; the cost grows with the classes that can tie, not with a sample count.
+ * Stat "expected_calls" counts the launches.
+ */
+int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, const int32_t* truth,
+                              int64_t P, int32_t B, int64_t N, int mem_kind,
+                              double* expected_score_out, double* hit_prob_out);
+
+/*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
  * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
@@ -389,7 +416,7 @@ int scv_host_free(void* p);
  * sort per problem -- queued, that is: a DEVICE-mode launch may find budgets it does not serve and leave them to the kernel behind it), "prefix_tokens" (launches of
  * scv_sort_prefix2<true>: the token sums of pools of 68 .. 128 votes out of token steps of the sort kernel's launch), "host_small_calls" / "host_pipelined_calls" (HOST-mode calls served by the one-block small path / by
  * the staging pipeline), "host_thread_start_failures" (worker threads of the staging pipeline the system refused to start: the
- * pipeline runs with the threads it has, the calling thread at least), "resample_calls" (launches of scv_resample_prefix_i32). */
+ * pipeline runs with the threads it has, the calling thread at least), "resample_calls" (launches of scv_resample_prefix_i32), "expected_calls" (launches of scv_expected_majority_i32). */
 int scv_get_stat(scv_ctx* ctx, const char* key, int64_t* out);
 
 int scv_device_count(void);

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -180,6 +181,8 @@ struct scv_ctx {
     int small_call_kb = 1024;       // option "host_small_kb": calls whose inputs + outputs fit in this many KiB take the small path (0: never)
     int64_t stat_small_calls = 0, stat_pipelined_calls = 0;
     int64_t stat_resample_calls = 0;    // scv_resample_prefix_i32 calls that launched the kernel
+    int64_t stat_expected_calls = 0;    // scv_expected_majority_i32 launches
+    double* d_expected_tab = nullptr;   // scv::kExpectedTabWords: binomials and Gauss-Legendre points (written at scv_create)
 };
 
 namespace {
@@ -1093,6 +1096,8 @@ int ensure_stage(scv_ctx* ctx, size_t bytes) {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+const std::vector<double>& expected_table();     // scv_expected_majority_i32's binomials and Gauss-Legendre points (below)
+
 }  // namespace
 
 extern "C" {
@@ -1134,8 +1139,13 @@ int scv_create(scv_ctx** out, int device, uint32_t flags) {
         if (e == hipSuccess) e = hipMalloc(&ctx->d_tickets, kTicketWords * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(ctx->d_tickets, 0, kTicketWords * sizeof(uint32_t));
         if (e == hipSuccess) { ctx->d_tickets_words = kTicketWords; e = hipDeviceSynchronize(); }
+        const std::vector<double>& tab = expected_table();
+        if (e == hipSuccess) { e = hipMalloc((void**)&ctx->d_expected_tab, tab.size() * sizeof(double)); }
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_expected_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) {
             int code = fail(-(int)e, "scv_create: %s", hipGetErrorString(e));
+            if (ctx->d_expected_tab) (void)hipFree(ctx->d_expected_tab);
             if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
             if (ctx->d_err) (void)hipFree(ctx->d_err);
             if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
@@ -1164,6 +1174,7 @@ int scv_destroy(scv_ctx* ctx) {
         if (ctx->small_d) (void)hipFree(ctx->small_d);
         if (ctx->d_partial) (void)hipFree(ctx->d_partial);
         if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
+        if (ctx->d_expected_tab) (void)hipFree(ctx->d_expected_tab);
         if (ctx->d_cells) (void)hipFree(ctx->d_cells);
         if (ctx->d_err) (void)hipFree(ctx->d_err);
         if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1544,7 +1555,7 @@ int launch_resample(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, co
         if (per_cu * lanes > best_per_cu * best_lanes) { best_lanes = lanes; best_np = (int)np; best_per_cu = per_cu; best_lds = lds; }
     }
     if (!best_lanes) return fail(SCV_ERR_ARG, "resample: N=%lld B=%d does not fit the LDS of one workgroup", (long long)N, B);
-    scv::ResampleArgs a;
+    scv::ResampleArgs a{};                                  // mode kResampleModeShuffle; the exact form's fields stay NULL
     a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
     a.P = P; a.p_offset = p_offset; a.seed = seed;
     a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M; a.np_max = best_np;
@@ -1644,6 +1655,115 @@ int resample_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, cons
         SCV_HIP(hipStreamSynchronize(s));
     }
     return check_err_word(ctx, w);
+}
+
+// The table of scv_expected_majority_i32 (scv::kExpectedTabWords doubles): C(n, i) for n <= 256 by Pascal's rule (every entry a sum of two
+// nonnegative terms: relative error <= n * 2^-53), then the Gauss-Legendre rules of 1 .. 64 points mapped to [0, 1] (Newton on P_Q in long double).
+void build_expected_table(std::vector<double>& t) {
+    t.assign(scv::kExpectedTabWords, 0.0);
+    for (int n = 0; n <= 256; ++n) {
+        double* row = t.data() + n * (n + 1) / 2;
+        const double* up = t.data() + (n - 1) * n / 2;
+        row[0] = row[n] = 1.0;
+        for (int i = 1; i < n; ++i) row[i] = up[i - 1] + up[i];
+    }
+    const long double pi = 3.141592653589793238462643383279502884L;
+    for (int Q = 1; Q <= scv::kExpectedMaxQ; ++Q) {
+        double* rule = t.data() + scv::kExpectedBinomWords + Q * (Q - 1);
+        for (int q = 0; q < Q; ++q) {
+            long double x = -cosl(pi * (q + 0.75L) / (Q + 0.5L)), dp = 1.0L;      // ascending nodes
+            for (int it = 0; it < 30; ++it) {
+                long double p0 = 1.0L, p1 = x;
+                for (int n = 2; n <= Q; ++n) { const long double p2 = ((2 * n - 1) * x * p1 - (n - 1) * p0) / n; p0 = p1; p1 = p2; }
+                dp = Q * (x * p1 - p0) / (x * x - 1.0L);
+                const long double dx = p1 / dp;
+                x -= dx;
+                if (fabsl(dx) < 1e-18L) break;
+            }
+            long double p0 = 1.0L, p1 = x;
+            for (int n = 2; n <= Q; ++n) { const long double p2 = ((2 * n - 1) * x * p1 - (n - 1) * p0) / n; p0 = p1; p1 = p2; }
+            dp = Q * (x * p1 - p0) / (x * x - 1.0L);
+            rule[2 * q] = (double)((1.0L + x) / 2.0L);
+            rule[2 * q + 1] = (double)(1.0L / ((1.0L - x * x) * dp * dp));          // 2 / ((1 - x^2) P'(x)^2), halved for [0, 1]
+        }
+    }
+}
+
+// The table, built once per process.
+const std::vector<double>& expected_table() {
+    static const std::vector<double> tab = [] { std::vector<double> t; build_expected_table(t); return t; }();
+    return tab;
+}
+
+
+// scv_expected_majority_i32 on device pointers: the expected-mode body of scv_resample_prefix<false> (scvote_expected.hip.h), one workgroup
+// of kExpectedLanes lanes per problem, persistent grid.  Overwrites score / hit rows [P, B].
+int launch_expected(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, const int32_t* truth, int64_t P, int32_t B, int64_t N,
+                    double* score, double* hit, uint32_t* err) {
+    if (P == 0) return SCV_OK;
+    const scv::ResampleFn fn = pick_resample_kernel(false);
+    const size_t lds = (size_t)scv::expected_lds_bytes(scv::kExpectedLanes);
+    int per_cu = 0;
+    SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), scv::kExpectedLanes, lds));
+    if (per_cu < 1) per_cu = 1;
+    scv::ResampleArgs a{};
+    a.pool = pool; a.n_valid = n_valid; a.truth = truth;
+    a.P = P; a.N = (int32_t)N; a.B = B;
+    a.err_flag = err;
+    a.mode = scv::kResampleModeExpected;
+    a.tab = ctx->d_expected_tab;
+    a.score_out = score; a.hit_out = hit;
+    int64_t grid = (int64_t)ctx->num_cus * per_cu;
+    if (grid > P) grid = P;
+    if (ctx->grid_override > 0) grid = ctx->grid_override;
+    EventPair* ev = nullptr;
+    if (int rc = next_event_pair(ctx, &ev)) return rc;
+    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)scv::kExpectedLanes), lds, ctx->stream, a);
+    SCV_HIP(hipGetLastError());
+    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
+    ctx->stat_expected_calls += 1;
+    ctx->err_dirty = true;
+    return SCV_OK;
+}
+
+// HOST mode: chunks of problems staged through the context's device buffer (inputs, outputs, error word), one launch, one download, one
+// stream sync per chunk; the error bits of every chunk are collected and reported at the end.
+int expected_host(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, const int32_t* truth, int64_t P, int32_t B, int64_t N,
+                  double* score_out, double* hit_out) {
+    const size_t row_bytes = (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (size_t)B * sizeof(double) * (hit_out ? 2 : 1);
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
+    size_t off = 0;
+    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
+    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
+    const size_t o_nv = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
+    const size_t o_score = off; off = align_up(off + (size_t)chunk * B * sizeof(double), 256);
+    const size_t o_hit = off; off = align_up(off + (hit_out ? (size_t)chunk * B * sizeof(double) : 0), 256);
+    const size_t o_err = off; off += 256;
+    if (int rc = ensure_stage(ctx, off)) return rc;
+    char* db = static_cast<char*>(ctx->d_stage);
+    hipStream_t s = ctx->stream;
+    SCV_HIP(hipMemcpyAsync(db + o_nv, n_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    uint32_t w_all = 0;
+    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
+        const int64_t np = std::min<int64_t>(chunk, P - p0);
+        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemsetAsync(db + o_err, 0, sizeof(uint32_t), s));
+        if (int rc = launch_expected(ctx, reinterpret_cast<const int32_t*>(db + o_pool), reinterpret_cast<const int32_t*>(db + o_nv),
+                                     reinterpret_cast<const int32_t*>(db + o_truth), np, B, N, reinterpret_cast<double*>(db + o_score),
+                                     hit_out ? reinterpret_cast<double*>(db + o_hit) : nullptr, reinterpret_cast<uint32_t*>(db + o_err))) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        uint32_t w = 0;
+        SCV_HIP(hipMemcpyAsync(score_out + p0 * B, db + o_score, (size_t)np * B * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (hit_out) SCV_HIP(hipMemcpyAsync(hit_out + p0 * B, db + o_hit, (size_t)np * B * sizeof(double), hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipStreamSynchronize(s));
+        w_all |= w;
+    }
+    return check_err_word(ctx, w_all);
 }
 }  // namespace
 
@@ -1771,6 +1891,24 @@ int scv_resample_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
     });
 }
 
+int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, const int32_t* truth, int64_t P, int32_t B,
+                              int64_t N, int mem_kind, double* expected_score_out, double* hit_prob_out) {
+    return guarded([&]() -> int {
+        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
+        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40))
+            return fail(SCV_ERR_ARG, "expected_majority: bad shape P=%lld B=%d N=%lld (1 <= N <= %d, 1 <= B <= %d, P >= 0)",
+                        (long long)P, B, (long long)N, scv::kResampleMaxN, scv::kResampleMaxB);
+        if (!n_valid || !expected_score_out) return fail(SCV_ERR_ARG, "expected_majority: n_valid and expected_score_out are required");
+        if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "expected_majority: pool and truth are required");
+        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        if (P == 0) return SCV_OK;
+        SCV_ENTER(ctx);
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_expected(ctx, pool, n_valid, truth, P, B, N, expected_score_out, hit_prob_out, ctx->d_err);
+        return expected_host(ctx, pool, n_valid, truth, P, B, N, expected_score_out, hit_prob_out);
+    });
+}
+
 int scv_synth_fill_i32(scv_ctx* ctx, int32_t* answers, int32_t* tokens, int32_t* truth, int64_t P, int32_t B,
                        int64_t N, int64_t p_offset, uint64_t seed, int dist) {
     return guarded([&]() -> int {
@@ -1875,6 +2013,7 @@ int scv_get_stat(scv_ctx* ctx, const char* key, int64_t* out) {
         else if (!strcmp(key, "host_small_calls")) *out = ctx->stat_small_calls;
         else if (!strcmp(key, "host_pipelined_calls")) *out = ctx->stat_pipelined_calls;
         else if (!strcmp(key, "resample_calls")) *out = ctx->stat_resample_calls;
+        else if (!strcmp(key, "expected_calls")) *out = ctx->stat_expected_calls;
         else if (!strcmp(key, "host_thread_start_failures")) *out = ctx->pipe ? ctx->pipe->pool.start_failures : 0;
         else return fail(SCV_ERR_ARG, "unknown stat '%s'", key);
         return SCV_OK;

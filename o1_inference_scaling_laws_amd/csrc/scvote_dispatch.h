@@ -76,8 +76,24 @@ struct ResampleArgs {
     int32_t N, B, R, r_begin, M, np_max;                 // np_max: problem rows a workgroup's chunk of lanes can touch
     unsigned long long* tie_hits; unsigned long long* token_sum; unsigned long long* truth_sum; unsigned long long* per_resample;
     uint32_t* err_flag;
+    // appended for the exact form (scv_expected_majority_i32, scvote_expected.hip.h); mode 0 is the shuffle above
+    int32_t mode;
+    const double* tab;                                   // kExpectedTabWords doubles of the context: binomials | Gauss-Legendre nodes
+    double* score_out; double* hit_out;                  // [P, B]; hit_out may be NULL
 };
 using ResampleFn = void (*)(const ResampleArgs);
+constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1;
+// the context's table: C(n, i) at n (n + 1) / 2 + i (0 <= i <= n <= 256), then for Q = 1 .. 64 Gauss-Legendre points on [0, 1],
+// (node, weight) pairs of rule Q at kExpectedBinomWords + Q (Q - 1) + 2 q
+constexpr int kExpectedMaxQ = 64;
+constexpr int kExpectedBinomWords = 257 * 258 / 2;
+constexpr int kExpectedTabWords = kExpectedBinomWords + kExpectedMaxQ * (kExpectedMaxQ + 1);
+constexpr int kExpectedLanes = 256;
+constexpr int kExpectedVec = 256 + 8;                     // 256 coefficients, one pad double per 32
+constexpr int kExpectedZeros = 136;                       // zeros in front: the slots of coefficients -129 .. -1 (a factor's degree is <= 128)
+// LDS bytes of a workgroup of `lanes` lanes: vectors [waves][kExpectedZeros + kExpectedVec] | E and H sums [2][waves][32] (doubles), then the int32 words:
+// votes per code [256] | classes per count [260] (hist[257]: the largest count) | meta [4] | the row's codes [64] | encoding scratch [64]
+constexpr long long expected_lds_bytes(int lanes) { return 8LL * ((lanes / 64) * (kExpectedZeros + kExpectedVec) + 2 * (lanes / 64) * 32) + 4LL * (256 + 260 + 4 + 64 + 64); }
 constexpr int kResampleMaxN = 256, kResampleMaxB = 32, kResampleMaxLanes = 256;
 // LDS words of a workgroup of `lanes` lanes (the kernel's layout, in this order): per-budget sums (2 B int64) | tie classes [B][N + 1] |
 // sorted budgets and their order (2 x 32) | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |

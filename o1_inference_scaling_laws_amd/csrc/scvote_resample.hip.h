@@ -28,6 +28,7 @@
 //    workgroup.  No scratch buffer, no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
 //
 // LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
+// The <false> instantiation has a second body, the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h).
 #pragma once
 
 #include "scvote_kernels.hip.h"
@@ -96,9 +97,18 @@ __device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64
     return bad;
 }
 
+}  // namespace scv
+
+#include "scvote_expected.hip.h"
+
+namespace scv {
+
 template <bool TOK>
 __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const ResampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem_wg[];
+    if constexpr (!TOK) {
+        if (a.mode == kResampleModeExpected) { expected_majority_body(a, smem_wg); return; }    // the exact form: scvote_expected.hip.h
+    }
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lanes = (int)blockDim.x, nwaves = lanes >> 6;
     const int lanes_log2 = 31 - __clz(lanes);

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import TIE_CLASSES, check
+from .expected import ExpectedResult
 from .resample import ResampleResult
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
@@ -290,6 +291,31 @@ class Engine:
                                               _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
         return ResampleResult(P, R, tie, tok, tcs, per)
 
+    def expected_majority(self, pool, truth, n_valid, tokens=None, hit_prob: bool = True) -> ExpectedResult:
+        """Exact expected majority vote over all k-subsets of each pool (scv_expected_majority_i32; CPU statement: expected.py).
+        pool int32 [P, N] (numpy, N <= 256), truth [P], n_valid int32 [B] (B <= 32).  ``tokens`` [P, N] only feeds
+        avg_tokens_used (the expected tokens of a k-subset need no kernel).  Blocking; no seed, nothing sampled."""
+        pool = np.ascontiguousarray(pool, dtype=np.int32)
+        if pool.ndim != 2:
+            raise ValueError("pool must be [P, N]")
+        P, N = pool.shape
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
+        if truth.shape != (P,) or n_valid.ndim != 1:
+            raise ValueError("truth must be [P] and n_valid [B]")
+        B = n_valid.shape[0]
+        token_total = None
+        if tokens is not None:
+            tokens = np.asarray(tokens)
+            if tokens.shape != pool.shape:
+                raise ValueError("tokens must match pool")
+            token_total = int(tokens.astype(np.int64).sum())
+        score = np.zeros((P, B), dtype=np.float64)
+        hit = np.zeros((P, B), dtype=np.float64) if hit_prob else None
+        check(self._L.scv_expected_majority_i32(self._ctx, _np_ptr(pool), _np_ptr(n_valid), _np_ptr(truth), P, B, N, _lib.MEM_HOST,
+                                                _np_ptr(score), _np_ptr(hit)))
+        return ExpectedResult(score, hit, np.clip(n_valid.astype(np.int64), 0, N), N, token_total)
+
     # ---- DEVICE mode (torch tensors; asynchronous on torch's current stream) --------------------
 
     def _device_call(self, votes, votes_name, row_shape, truth, tokens, n_valid, counters, cells, cell_tokens, overwrite, want_no_cells=True):
@@ -453,6 +479,36 @@ class Engine:
                                               seed, M if M is not None else 1, _lib.MEM_DEVICE, ptr(tie_class_hits), ptr(token_sum),
                                               ptr(truth_count_sum), ptr(per_resample)))
         return tie_class_hits, token_sum, truth_count_sum, per_resample
+
+    def expected_majority_device(self, pool, truth, n_valid, score=None, hit_prob=None, want_hit_prob: bool = True):
+        """DEVICE-mode expected_majority: pool torch.int32 cuda [P, N], truth [P], n_valid [B] (read on the device).  OVERWRITES
+        score / hit_prob (float64 [P, B]; allocated when None -- hit_prob only when ``want_hit_prob``).  Runs on torch's current stream,
+        does not synchronise, may be captured into a graph (with the outputs given).  Returns (score, hit_prob)."""
+        import torch
+        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
+            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
+        self._check_device(pool, "pool")
+        P, N = int(pool.shape[0]), int(pool.shape[1])
+        dev = pool.device
+        B = int(n_valid.shape[0])
+        for name, t, shape in (("truth", truth, (P,)), ("n_valid", n_valid, (B,))):
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
+
+        def buf(t, name):
+            if t is None:
+                return torch.empty((P, B), dtype=torch.float64, device=dev)
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (P, B) and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA float64 tensor {(P, B)} on {dev}")
+            return t
+        score = buf(score, "score")
+        if hit_prob is not None or want_hit_prob:
+            hit_prob = buf(hit_prob, "hit_prob")
+        self.use_torch_stream()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self._L.scv_expected_majority_i32(self._ctx, ptr(pool), ptr(n_valid), ptr(truth), P, B, N, _lib.MEM_DEVICE, ptr(score),
+                                                ptr(hit_prob)))
+        return score, hit_prob
 
 
 class MultiDeviceEngine:
