@@ -7,6 +7,7 @@
 #pragma once
 
 #include "scvote_kernels.hip.h"
+#include "scvote_expected_table.h"
 
 namespace scv {
 
@@ -83,11 +84,7 @@ struct ResampleArgs {
 };
 using ResampleFn = void (*)(const ResampleArgs);
 constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1;
-// the context's table: C(n, i) at n (n + 1) / 2 + i (0 <= i <= n <= 256), then for Q = 1 .. 64 Gauss-Legendre points on [0, 1],
-// (node, weight) pairs of rule Q at kExpectedBinomWords + Q (Q - 1) + 2 q
-constexpr int kExpectedMaxQ = 64;
-constexpr int kExpectedBinomWords = 257 * 258 / 2;
-constexpr int kExpectedTabWords = kExpectedBinomWords + kExpectedMaxQ * (kExpectedMaxQ + 1);
+// the context's table (kExpectedTabWords doubles: binomials | Gauss-Legendre rules) and its layout: scvote_expected_table.h
 constexpr int kExpectedLanes = 256;
 constexpr int kExpectedVec = 256 + 8;                     // 256 coefficients, one pad double per 32
 constexpr int kExpectedZeros = 136;                       // zeros in front: the slots of coefficients -129 .. -1 (a factor's degree is <= 128)

@@ -25,7 +25,8 @@
 //    a boundary the wave adds its lanes' hits to the workgroup's LDS tables (one ballot for the common n_modes == 1, an LDS atomic
 //    for the rest), its truth-count and token sums (DPP reductions), and -- when requested -- each hit to per_resample with one
 //    global atomic (lanes of a wave hold different resamples).  The tables are flushed with non-returning int64 atomics once per
-//    workgroup.  No scratch buffer, no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
+//    workgroup (the 32-bit tie table also every floor((2^32 - 1) / lanes) chunks of it, so that no counter wraps).  No scratch buffer,
+//    no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
 //
 // LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
 // The <false> instantiation has a second body, the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h).
@@ -148,7 +149,13 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
     const int64_t nchunks = (total + lanes - 1) / lanes;
     const uint32_t lane_byte = (uint32_t)tid << 2;
     bool bad = false, overflow = false;
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    // A chunk adds at most `lanes` to one tie counter (one per lane and budget), and P * R may reach 2^62 with one workgroup doing all:
+    // the workgroup's chunks go in epochs of floor((2^32 - 1) / lanes), and the 32-bit table is flushed into the int64 outputs between
+    // two epochs, before any counter can wrap.
+    const int64_t epoch = (int64_t)(0xffffffffu / (uint32_t)lanes) * gridDim.x;
+    for (int64_t c0 = blockIdx.x; c0 < nchunks; c0 += epoch) {
+    const int64_t c1 = nchunks - c0 > epoch ? c0 + epoch : nchunks;
+    for (int64_t chunk = c0; chunk < c1; chunk += gridDim.x) {
         const int64_t t0 = chunk * lanes;
         const int64_t p_lo = t0 / R;
         int64_t p_hi = (t0 + lanes - 1) / R;
@@ -211,6 +218,14 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
             }
         }
         __syncthreads();                                                              // the rows are rewritten by the next chunk
+    }
+    if (c1 < nchunks) {                                                               // another epoch follows (uniform)
+        for (int i = tid; i < B * TC; i += lanes) {
+            const uint32_t v = tie[i];
+            if (v) { atomicAdd(&a.tie_hits[(int64_t)(i / TC) * SCV_TIE_CLASSES + (i % TC)], (unsigned long long)v); tie[i] = 0u; }
+        }
+        __syncthreads();
+    }
     }
     if (__ballot(bad) && lane == 0) atomicOr(a.err_flag, 1u);
     if (__ballot(overflow) && lane == 0) atomicOr(a.err_flag, 2u);

@@ -5,11 +5,12 @@ problem's pool -- the limit of resample.py's shuffles as R grows without bound. 
   integers in the DP over (s, u) and rationals only at the end.  It uses the small-class fold and the no-tie closed form, and the
   e_s recurrence for j = 1, so N = 256 stays in seconds.
 * ``expected_majority_quadrature`` -- the GPU's algorithm in numpy float64: the same work items (j, Gauss-Legendre point), the same
-  identities, numpy.polynomial.legendre.leggauss points.  The tests pin it to the rationals; it is where the kernel's bookkeeping was
+  identities, the kernel's own Gauss-Legendre rules (``_gl01``).  The tests pin it to the rationals; it is where the kernel's bookkeeping was
   rehearsed.
 * ``ExpectedResult`` -- what Engine.expected_majority returns."""
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 from fractions import Fraction
@@ -156,9 +157,35 @@ def expected_majority_exact(pool, truth, n_valid):
     return E, H
 
 
+@functools.lru_cache(maxsize=None)
 def _gl01(Q: int):
-    x, w = np.polynomial.legendre.leggauss(Q)
-    return (1.0 + x) / 2.0, w / 2.0
+    """The kernel's Gauss-Legendre rule of Q points on [0, 1] (build_expected_table in csrc/scvote_expected_table.h, step for step):
+    Newton on P_Q from x = -cos(pi (q + 3/4) / (Q + 1/2)) in np.longdouble -- the x86-64 C long double, so the same roundings and the
+    same table bits (tests/test_expected_table.py).  numpy's leggauss weights are off by up to 2e-12 relative for Q >= 40.
+    Returns (nodes ascending, weights), float64 [Q] each."""
+    ld = np.longdouble
+    one, pi = ld(1), ld("3.141592653589793238462643383279502884")
+    ys, ws = np.empty(Q), np.empty(Q)
+
+    def legendre(x):
+        p0, p1 = one, x
+        for n in range(2, Q + 1):
+            p0, p1 = p1, (ld(2 * n - 1) * x * p1 - ld(n - 1) * p0) / ld(n)
+        return p0, p1, ld(Q) * (x * p1 - p0) / (x * x - one)
+
+    for q in range(Q):
+        x = -np.cos(pi * (ld(q) + ld("0.75")) / (ld(Q) + ld("0.5")))
+        for _ in range(30):
+            _p0, p1, dp = legendre(x)
+            dx = p1 / dp
+            x = x - dx
+            if abs(dx) < ld("1e-18"):
+                break
+        _p0, _p1, dp = legendre(x)
+        ys[q] = np.float64((one + x) / ld(2))
+        ws[q] = np.float64(one / ((one - x * x) * dp * dp))
+    ys.flags.writeable = ws.flags.writeable = False
+    return ys, ws
 
 
 def work_items(N: int, ct: int, others, kmax: int, hit: bool = True):
