@@ -292,6 +292,48 @@ int scv_resample_prefix_i32(scv_ctx* ctx,
                             int64_t* truth_count_sum_out, int64_t* per_resample_out);
 
 /*
+ * Token-budget majority vote: the vote over the longest prefix of a pool ordering that fits a budget of TOKENS (new semantics, not in the
+ * reference; its maj@N tail buys N = T // 2^11 samples whatever they cost, o1.py:274-277).
+ *   pool / tokens  int32 [P, N] (both required; a negative token count is an error); token_budget int64 [B] (required, any order,
+ *   duplicates fine); truth int32 [P]
+ * For problem p (global index pg = p_offset + p), an ordering pi and budget T_b:
+ *   n_b    = max { n <= N : sum_{i<n} tokens[p, pi(i)] <= T_b }   voting stops at the first sample that does not fit (later, cheaper
+ *            samples are not skipped to); samples of 0 tokens always fit; a negative T_b gives an empty prefix
+ *   cell (p, pi, b) = statistics.multimode over pool[p, pi(0 : n_b)], scored as everywhere (1 / n_modes on a hit; an empty prefix has
+ *            no hit); its tokens sum_{i<n_b} tokens[p, pi(i)] <= T_b
+ *   order  SCV_ORDER_POOL (0): pi is the identity, the cache order (one draw): r_begin = 0, r_end = 1 required
+ *          SCV_ORDER_SHUFFLED (1): pi is EXACTLY the partial Fisher-Yates permutation of scv_resample_prefix_i32 for (seed, pg, r),
+ *          r in [r_begin, r_end)
+ * Votes and truths follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at
+ * scv_sync in DEVICE mode) or counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.  A negative token
+ * count sets error bit 4: SCV_ERR_ARG at the call in HOST mode, at scv_sync in DEVICE mode.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
+ *   token_sum_out        int64 [B]        (NULL ok) tokens actually spent
+ *   vote_count_sum_out   int64 [B]        (NULL ok) sum of n_b
+ *   truth_count_sum_out  int64 [B]        (NULL ok) votes equal to the truth in the prefixes
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) class counts per ordering, summed over problems only (m < M; a hit with
+ *                        n_modes >= M sets error bit 1: SCV_ERR_ARG at scv_sync)
+ *   cells_out            scv_cell [P, B] (NULL ok; SCV_ORDER_POOL only) and cell_tokens_out int64 [P, B] (NULL ok; SCV_ORDER_POOL
+ *                        only): the cells of the cache order, as scv_aggregate_prefix_i32 writes them; OVERWRITTEN in both modes
+ * DEVICE mode ACCUMULATES into the per-budget outputs and per_resample (+=) and only enqueues: no allocation, no synchronisation, legal
+ * under hipGraph capture.  HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices of r and shards of p
+ * (p_offset) add up to the whole call bit for bit.  Limits: 1 <= N <= 256, 1 <= B <= 32, 0 <= r_begin <= r_end, p_offset >= 0, M >= 1
+ * when per_resample_out is given; anything else -- a bad order, SCV_ORDER_POOL with r-range other than [0, 1), cell outputs with
+ * SCV_ORDER_SHUFFLED -- is SCV_ERR_ARG.  One lane per (problem, ordering) walks until its largest budget is spent
+ * (csrc/scvote_budget.hip.h).  Stat "token_budget_calls" counts the launches.
+ */
+#define SCV_ORDER_POOL 0
+#define SCV_ORDER_SHUFFLED 1
+int scv_token_budget_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens,
+                                const int64_t* token_budget, const int32_t* truth,
+                                int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                                int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                                int64_t* tie_class_hits_out, int64_t* token_sum_out,
+                                int64_t* vote_count_sum_out, int64_t* truth_count_sum_out,
+                                int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out);
+
+/*
  * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
  * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
  * seed and nothing left to converge.
@@ -320,7 +362,7 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
 
 /*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the
@@ -416,7 +458,8 @@ int scv_host_free(void* p);
  * sort per problem -- queued, that is: a DEVICE-mode launch may find budgets it does not serve and leave them to the kernel behind it), "prefix_tokens" (launches of
  * scv_sort_prefix2<true>: the token sums of pools of 68 .. 128 votes out of token steps of the sort kernel's launch), "host_small_calls" / "host_pipelined_calls" (HOST-mode calls served by the one-block small path / by
  * the staging pipeline), "host_thread_start_failures" (worker threads of the staging pipeline the system refused to start: the
- * pipeline runs with the threads it has, the calling thread at least), "resample_calls" (launches of scv_resample_prefix_i32), "expected_calls" (launches of scv_expected_majority_i32). */
+ * pipeline runs with the threads it has, the calling thread at least), "resample_calls" (launches of scv_resample_prefix_i32), "expected_calls" (launches of scv_expected_majority_i32), "token_budget_calls" (launches of
+ * scv_token_budget_prefix_i32). */
 int scv_get_stat(scv_ctx* ctx, const char* key, int64_t* out);
 
 int scv_device_count(void);

@@ -183,6 +183,7 @@ struct scv_ctx {
     int64_t stat_small_calls = 0, stat_pipelined_calls = 0;
     int64_t stat_resample_calls = 0;    // scv_resample_prefix_i32 calls that launched the kernel
     int64_t stat_expected_calls = 0;    // scv_expected_majority_i32 launches
+    int64_t stat_token_budget_calls = 0;    // scv_token_budget_prefix_i32 launches
     double* d_expected_tab = nullptr;   // scv::kExpectedTabWords: binomials and Gauss-Legendre points (written at scv_create)
 };
 
@@ -1069,6 +1070,7 @@ int check_err_word(scv_ctx* ctx, uint32_t w) {
     if ((w & 1u) && !(ctx->flags & SCV_FLAG_CLAMP_TO_INVALID_BIN))
         return fail(SCV_ERR_DOMAIN, "a vote outside bins 0..1023 was seen; results are invalid");
     if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap / resample: a hit had n_modes >= M");
+    if (w & 16u) return fail(SCV_ERR_ARG, "token_budget: a token count was negative; results are invalid");
     if (w & 8u) return fail(SCV_ERR_ARG, "prefix_path = 5 promised budgets that are 0, a power of two or >= N: the list in n_valid is not; nothing was computed");
     return SCV_OK;
 }
@@ -1533,38 +1535,27 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
 }
 
 
-// scv_resample_prefix_i32 on device pointers: one launch of scv_resample_prefix<tok> (scvote_resample.hip.h), accumulating into the outputs.
-// Workgroups of 256 / 128 / 64 lanes: the one that keeps the most waves resident per CU (LDS: 2 * 4 * ceil(N / 4) bytes per lane + the
-// problem rows a chunk touches + the per-budget tables), the larger on a tie (fewer tables to flush).  Persistent grid.
-int launch_resample(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
-                    int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
-                    int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    if (P == 0 || R == 0) return SCV_OK;
-    const bool tok = tokens != nullptr;
-    const scv::ResampleFn fn = pick_resample_kernel(tok);
+// One launch of a lane-per-(problem, ordering) body of scv_resample_prefix (the shuffle, scvote_resample.hip.h; the token budgets,
+// scvote_budget.hip.h): a.P, a.R, a.N, a.B and the body's fields are set by the caller, a.np_max here.  Workgroups of 256 / 128 / 64 lanes:
+// the one that keeps the most waves resident per CU (LDS: lds_words(lanes, rows a chunk touches) words -- the lanes' byte arrays, the
+// problem rows, the per-budget tables), the larger on a tie (fewer tables to flush).  Persistent grid.  `what` prefixes the error message.
+template <class LdsWords>
+int launch_lane_body(scv_ctx* ctx, scv::ResampleFn fn, scv::ResampleArgs& a, LdsWords lds_words, const char* what, int64_t* stat_calls) {
+    const int64_t P = a.P, R = a.R;
     SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
     int best_lanes = 0, best_np = 0, best_per_cu = 0;
     size_t best_lds = 0;
     for (int lanes = scv::kResampleMaxLanes; lanes >= 64; lanes >>= 1) {
         const int64_t np = std::min<int64_t>(P, (lanes - 1) / R + 2);
-        const size_t lds = (size_t)scv::resample_lds_words((int)N, B, lanes, (int)np) * sizeof(uint32_t);
+        const size_t lds = (size_t)lds_words(lanes, (int)np) * sizeof(uint32_t);
         if ((int64_t)lds > ctx->lds_max) continue;
         int per_cu = 0;
         SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds));
         if (per_cu < 1) continue;
         if (per_cu * lanes > best_per_cu * best_lanes) { best_lanes = lanes; best_np = (int)np; best_per_cu = per_cu; best_lds = lds; }
     }
-    if (!best_lanes) return fail(SCV_ERR_ARG, "resample: N=%lld B=%d does not fit the LDS of one workgroup", (long long)N, B);
-    scv::ResampleArgs a{};                                  // mode kResampleModeShuffle; the exact form's fields stay NULL
-    a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
-    a.P = P; a.p_offset = p_offset; a.seed = seed;
-    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M; a.np_max = best_np;
-    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
-    a.token_sum = tok ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
-    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
-    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
-    a.err_flag = err;
+    if (!best_lanes) return fail(SCV_ERR_ARG, "%s: N=%d B=%d does not fit the LDS of one workgroup", what, a.N, a.B);
+    a.np_max = best_np;
     const int64_t nchunks = (P * R + best_lanes - 1) / best_lanes;
     int64_t grid = (int64_t)ctx->num_cus * best_per_cu;
     if (grid > nchunks) grid = nchunks;
@@ -1575,9 +1566,29 @@ int launch_resample(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, co
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)best_lanes), best_lds, ctx->stream, a);
     SCV_HIP(hipGetLastError());
     if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
-    ctx->stat_resample_calls += 1;
+    *stat_calls += 1;
     ctx->err_dirty = true;
     return SCV_OK;
+}
+
+// scv_resample_prefix_i32 on device pointers: one launch of scv_resample_prefix<tok> (scvote_resample.hip.h), accumulating into the outputs.
+int launch_resample(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
+                    int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                    int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    if (P == 0 || R == 0) return SCV_OK;
+    const bool tok = tokens != nullptr;
+    scv::ResampleArgs a{};                                  // mode kResampleModeShuffle; the other bodies' fields stay NULL
+    a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
+    a.P = P; a.p_offset = p_offset; a.seed = seed;
+    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
+    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
+    a.token_sum = tok ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
+    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
+    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
+    a.err_flag = err;
+    return launch_lane_body(ctx, pick_resample_kernel(tok), a,
+                            [&](int lanes, int np) { return scv::resample_lds_words((int)N, B, lanes, np); }, "resample", &ctx->stat_resample_calls);
 }
 
 // HOST mode: inputs and zeroed outputs in one device block behind one upload, the kernel, one download, one stream sync.  Calls that fit
@@ -1734,6 +1745,95 @@ int expected_host(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, con
     }
     return check_err_word(ctx, w_all);
 }
+
+// scv_token_budget_prefix_i32 on device pointers: one launch of the token-budget body of scv_resample_prefix<true> (scvote_budget.hip.h),
+// accumulating into the per-budget outputs and overwriting the cells.
+int launch_token_budget(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* budgets, const int32_t* truth,
+                        int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed,
+                        int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum, int64_t* truth_sum, int64_t* per_resample,
+                        scv_cell* cells, int64_t* cell_tokens, uint32_t* err) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    if (P == 0 || R == 0) return SCV_OK;
+    const bool shuffled = order == SCV_ORDER_SHUFFLED;
+    scv::ResampleArgs a{};
+    a.pool = pool; a.tokens = tokens; a.truth = truth;
+    a.P = P; a.p_offset = p_offset; a.seed = seed;
+    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
+    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
+    a.token_sum = reinterpret_cast<unsigned long long*>(tok_sum);
+    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
+    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
+    a.err_flag = err;
+    a.mode = scv::kResampleModeTokenBudget;
+    a.budgets = budgets;
+    a.order = shuffled ? scv::kOrderShuffled : scv::kOrderPool;
+    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
+    return launch_lane_body(ctx, pick_resample_kernel(true), a,
+                            [&](int lanes, int np) { return scv::token_budget_lds_words((int)N, B, lanes, np, shuffled); }, "token_budget",
+                            &ctx->stat_token_budget_calls);
+}
+
+// HOST mode: chunks of problems (pool, tokens, truth; the budgets once) staged through the context's device buffer.  The per-budget sums and
+// per_resample are zeroed once and accumulate over the chunks on the device; each chunk's cells come back behind its launch, one stream sync
+// per chunk (the next chunk overwrites the staged inputs).  The sums and the error word are downloaded once, at the end.
+int token_budget_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* budgets, const int32_t* truth, int64_t P,
+                      int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                      int64_t* tie_out, int64_t* tok_out, int64_t* votes_out, int64_t* tcs_out, int64_t* per_out, scv_cell* cells_out,
+                      int64_t* cell_tokens_out) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
+    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
+    const size_t row_bytes = 2 * (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (cells_out ? (size_t)B * sizeof(scv_cell) : 0) +
+                             (cell_tokens_out ? (size_t)B * sizeof(int64_t) : 0);
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
+    size_t off = 0;
+    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
+    const size_t o_tok = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
+    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
+    const size_t o_bud = off; off = align_up(off + (size_t)B * sizeof(int64_t), 256);
+    const size_t o_cells = off; off = align_up(off + (cells_out ? (size_t)chunk * B * sizeof(scv_cell) : 0), 256);
+    const size_t o_ct = off; off = align_up(off + (cell_tokens_out ? (size_t)chunk * B * sizeof(int64_t) : 0), 256);
+    const size_t o_out = off;                                                        // tie | token sums | vote sums | truth sums | per_resample | error word
+    const size_t o_ts = o_out + tie_bytes, o_vs = o_ts + sums_bytes, o_tc = o_vs + sums_bytes, o_per = o_tc + sums_bytes;
+    const size_t o_err = align_up(o_per + per_bytes, 256);
+    const size_t total = o_err + 256;
+    if (int rc = ensure_stage(ctx, total)) return rc;
+    char* db = static_cast<char*>(ctx->d_stage);
+    hipStream_t s = ctx->stream;
+    SCV_HIP(hipMemcpyAsync(db + o_bud, budgets, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
+    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
+        const int64_t np = std::min<int64_t>(chunk, P - p0);
+        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemcpyAsync(db + o_tok, tokens + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (int rc = launch_token_budget(ctx, reinterpret_cast<const int32_t*>(db + o_pool), reinterpret_cast<const int32_t*>(db + o_tok),
+                                         reinterpret_cast<const int64_t*>(db + o_bud), reinterpret_cast<const int32_t*>(db + o_truth), np, B, N,
+                                         p_offset + p0, order, r_begin, r_end, seed, M, reinterpret_cast<int64_t*>(db + o_out),
+                                         reinterpret_cast<int64_t*>(db + o_ts), reinterpret_cast<int64_t*>(db + o_vs),
+                                         reinterpret_cast<int64_t*>(db + o_tc), per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
+                                         cells_out ? reinterpret_cast<scv_cell*>(db + o_cells) : nullptr,
+                                         cell_tokens_out ? reinterpret_cast<int64_t*>(db + o_ct) : nullptr,
+                                         reinterpret_cast<uint32_t*>(db + o_err))) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        if (cells_out) SCV_HIP(hipMemcpyAsync(cells_out + p0 * B, db + o_cells, (size_t)np * B * sizeof(scv_cell), hipMemcpyDeviceToHost, s));
+        if (cell_tokens_out)
+            SCV_HIP(hipMemcpyAsync(cell_tokens_out + p0 * B, db + o_ct, (size_t)np * B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipStreamSynchronize(s));
+    }
+    uint32_t w = 0;
+    SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
+    if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
+    if (votes_out) SCV_HIP(hipMemcpyAsync(votes_out, db + o_vs, sums_bytes, hipMemcpyDeviceToHost, s));
+    if (tcs_out) SCV_HIP(hipMemcpyAsync(tcs_out, db + o_tc, sums_bytes, hipMemcpyDeviceToHost, s));
+    if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipStreamSynchronize(s));
+    return check_err_word(ctx, w);
+}
 }  // namespace
 
 extern "C" {
@@ -1853,10 +1953,49 @@ int scv_resample_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
             memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
             if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
             if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
             return SCV_OK;
         }
         return resample_host(ctx, pool, tokens, n_valid, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out,
                              token_sum_out, truth_count_sum_out, per_resample_out);
+    });
+}
+
+int scv_token_budget_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* token_budget, const int32_t* truth,
+                                int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed,
+                                int32_t M, int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* vote_count_sum_out,
+                                int64_t* truth_count_sum_out, int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out) {
+    return guarded([&]() -> int {
+        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
+        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
+            return fail(SCV_ERR_ARG, "token_budget: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
+                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
+        if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "token_budget: bad order %d", order);
+        if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
+            return fail(SCV_ERR_ARG, "token_budget: SCV_ORDER_POOL is one draw: r_begin = 0, r_end = 1 (got [%d,%d))", r_begin, r_end);
+        if (order == SCV_ORDER_SHUFFLED && (cells_out || cell_tokens_out))
+            return fail(SCV_ERR_ARG, "token_budget: cells_out / cell_tokens_out are written in SCV_ORDER_POOL only");
+        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "token_budget: P * (r_end - r_begin) exceeds 2^62");
+        if (!token_budget || !tie_class_hits_out) return fail(SCV_ERR_ARG, "token_budget: token_budget and tie_class_hits_out are required");
+        if (P > 0 && (!pool || !tokens || !truth)) return fail(SCV_ERR_ARG, "token_budget: pool, tokens and truth are required");
+        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "token_budget: per_resample_out needs M >= 1 (got %d)", M);
+        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_token_budget(ctx, pool, tokens, token_budget, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
+                                       tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, per_resample_out, cells_out,
+                                       cell_tokens_out, ctx->d_err);
+        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing voted, all zero
+            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
+            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (vote_count_sum_out) memset(vote_count_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
+            return SCV_OK;
+        }
+        return token_budget_host(ctx, pool, tokens, token_budget, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie_class_hits_out,
+                                 token_sum_out, vote_count_sum_out, truth_count_sum_out, per_resample_out, cells_out, cell_tokens_out);
     });
 }
 
@@ -1983,6 +2122,7 @@ int scv_get_stat(scv_ctx* ctx, const char* key, int64_t* out) {
         else if (!strcmp(key, "host_pipelined_calls")) *out = ctx->stat_pipelined_calls;
         else if (!strcmp(key, "resample_calls")) *out = ctx->stat_resample_calls;
         else if (!strcmp(key, "expected_calls")) *out = ctx->stat_expected_calls;
+        else if (!strcmp(key, "token_budget_calls")) *out = ctx->stat_token_budget_calls;
         else if (!strcmp(key, "host_thread_start_failures")) *out = ctx->pipe ? ctx->pipe->pool.start_failures : 0;
         else return fail(SCV_ERR_ARG, "unknown stat '%s'", key);
         return SCV_OK;

@@ -81,9 +81,22 @@ struct ResampleArgs {
     int32_t mode;
     const double* tab;                                   // kExpectedTabWords doubles of the context: binomials | Gauss-Legendre nodes
     double* score_out; double* hit_out;                  // [P, B]; hit_out may be NULL
+    // appended for the token-budget vote (scv_token_budget_prefix_i32, scvote_budget.hip.h): n_valid is unused, tokens are required
+    const int64_t* budgets;                              // [B] token budgets, any order
+    int32_t order;                                       // kOrderPool (x = i, R = 1) | kOrderShuffled (the shuffle above)
+    unsigned long long* vote_sum;                        // [B] votes in the prefixes (NULL ok)
+    scv_cell* cells_out; int64_t* cell_tokens_out;       // [P, B] (NULL ok; pool order only), overwritten
 };
 using ResampleFn = void (*)(const ResampleArgs);
-constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1;
+constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2;
+constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
+// LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
+// budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
+// the rows as byte codes [np_max][N4] | the lanes' counts [N4][lanes] | their Fisher-Yates arrays [N4][lanes] (shuffled order only)
+constexpr long long token_budget_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
+    return 64 + 6LL * B + 32 + (long long)B * (N + 1) + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) +
+           (shuffled ? 2LL : 1LL) * lanes * ((N + 3) / 4);
+}
 // the context's table (kExpectedTabWords doubles: binomials | Gauss-Legendre rules) and its layout: scvote_expected_table.h
 constexpr int kExpectedLanes = 256;
 constexpr int kExpectedVec = 256 + 8;                     // 256 coefficients, one pad double per 32

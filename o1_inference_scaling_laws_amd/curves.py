@@ -4,7 +4,8 @@ scv_resample_prefix_i32).
 The reference's majority-vote tail (o1.py:266-277: T >= 2^11 votes over the first N = T // 2^11 samples of the 2^11-token pool)
 is one ordering of the cache.  ``expected_majority_records`` averages each point over ``resamples`` random orderings of the same
 pool and returns it in the reference's log schema, so plot_helpers can draw the smoothed tail next to the single-ordering one.
-``exact_majority_records`` gives the limit of that average -- the mean over all k-subsets -- with no seed and no resample count."""
+``exact_majority_records`` gives the limit of that average -- the mean over all k-subsets -- with no seed and no resample count.
+``token_budget_records`` ends each vote where a budget of TOKENS runs out instead of after a number of samples."""
 from __future__ import annotations
 
 import numpy as np
@@ -54,3 +55,16 @@ def exact_majority_records(engine, pool, truth, tokens, token_limits):
     res = engine.expected_majority(pool, truth, ns, tokens=tokens, hit_prob=False)
     return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
             for b, (t, _n) in enumerate(budgets)]
+
+
+def token_budget_records(engine, pool, truth, tokens, token_limits, resamples: int | None = None, seed: int = 0):
+    """pool / tokens int32 [P, Npool] (each problem's samples in cache order), truth int32 [P].  For every token limit T: the accuracy of
+    the majority vote over the longest prefix whose tokens fit T (Engine.token_budget_prefix, scv_token_budget_prefix_i32) -- in the
+    cache order (``resamples=None``, one draw) or averaged over ``resamples`` random orderings -- and the tokens it actually spent, as
+    records {'token_limit', 'accuracy', 'avg_tokens_used'} (o1.py:278-283).  Here token_limit is a real per-problem cap:
+    avg_tokens_used <= token_limit, so plot_helpers can draw the curve beside the maj@N tail on the same axis."""
+    limits = [int(t) for t in token_limits]
+    res = engine.token_budget_prefix(np.asarray(pool, dtype=np.int32), np.asarray(tokens, dtype=np.int32), truth,
+                                     np.array(limits, dtype=np.int64), resamples=resamples, seed=seed, M=0)
+    return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
+            for b, t in enumerate(limits)]

@@ -20,6 +20,7 @@ from . import _lib
 from ._lib import TIE_CLASSES, check
 from .expected import ExpectedResult
 from .resample import ResampleResult
+from .token_budget import TokenBudgetResult
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
 CELL_DTYPE = np.dtype(
@@ -316,6 +317,43 @@ class Engine:
                                                 _np_ptr(score), _np_ptr(hit)))
         return ExpectedResult(score, hit, np.clip(n_valid.astype(np.int64), 0, N), N, token_total)
 
+    def token_budget_prefix(self, pool, tokens, truth, token_budgets, resamples: int | None = None, seed: int = 0, r_begin: int = 0,
+                            p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> TokenBudgetResult:
+        """Majority vote over the longest prefix of each pool ordering that fits a token budget (scv_token_budget_prefix_i32; CPU mirror:
+        token_budget.py).  pool / tokens int32 [P, N] (numpy, N <= 256), truth [P], token_budgets int64 [B] (B <= 32, any order).
+        ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells and cell tokens); otherwise the orderings
+        r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of ``per_resample`` (None: N + 1, which no hit can exceed;
+        0: not computed).  Blocking."""
+        pool = np.ascontiguousarray(pool, dtype=np.int32)
+        if pool.ndim != 2:
+            raise ValueError("pool must be [P, N]")
+        P, N = pool.shape
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        budgets = np.ascontiguousarray(token_budgets, dtype=np.int64)
+        if tokens.shape != pool.shape or truth.shape != (P,) or budgets.ndim != 1:
+            raise ValueError("tokens must match pool, truth must be [P] and token_budgets [B]")
+        B = budgets.shape[0]
+        shuffled = resamples is not None
+        if want_cells and shuffled:
+            raise ValueError("cells are written in pool order only (resamples=None)")
+        r0, r1 = (int(r_begin), int(r_begin) + int(resamples)) if shuffled else (int(r_begin), int(r_begin) + 1)
+        R = r1 - r0
+        if M is None:
+            M = N + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64)
+        votes = np.zeros((B,), dtype=np.int64)
+        tcs = np.zeros((B,), dtype=np.int64)
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
+        cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
+        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+        check(self._L.scv_token_budget_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N,
+                                                  p_offset, order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok),
+                                                  _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
+        return TokenBudgetResult(P, R, tie, tok, votes, tcs, per, cells, cell_tokens)
+
     # ---- DEVICE mode (torch tensors; asynchronous on torch's current stream) --------------------
 
     def _device_call(self, votes, votes_name, row_shape, truth, tokens, n_valid, counters, cells, cell_tokens, overwrite, want_no_cells=True):
@@ -509,6 +547,59 @@ class Engine:
         check(self._L.scv_expected_majority_i32(self._ctx, ptr(pool), ptr(n_valid), ptr(truth), P, B, N, _lib.MEM_DEVICE, ptr(score),
                                                 ptr(hit_prob)))
         return score, hit_prob
+
+
+    def token_budget_prefix_device(self, pool, tokens, truth, token_budgets, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
+                                   p_offset: int = 0, tie_class_hits=None, token_sum=None, vote_count_sum=None, truth_count_sum=None,
+                                   per_resample=None, M: int | None = None, cells=None, cell_tokens=None, want_cells: bool = False):
+        """DEVICE-mode token_budget_prefix: pool / tokens torch.int32 cuda [P, N], truth [P], token_budgets torch.int64 [B].  ``r_end=None``:
+        the pool's own order (r_begin must be 0); otherwise the orderings [r_begin, r_end).  ACCUMULATES into the given int64 buffers
+        (tie_class_hits [B, 1025], token_sum, vote_count_sum, truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left None are
+        allocated zeroed -- per_resample only when ``M`` is given).  Pool order only: OVERWRITES cells (uint8 [P, B, 16]) and cell_tokens
+        (int64 [P, B]), allocated when ``want_cells``.  Runs on torch's current stream, does not synchronise.  Returns (tie_class_hits,
+        token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens)."""
+        import torch
+        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
+            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
+        self._check_device(pool, "pool")
+        P, N = int(pool.shape[0]), int(pool.shape[1])
+        dev = pool.device
+        B = int(token_budgets.shape[0])
+        for name, t, shape, dt in (("tokens", tokens, (P, N), torch.int32), ("truth", truth, (P,), torch.int32),
+                                   ("token_budgets", token_budgets, (B,), torch.int64)):
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {shape} on {dev}")
+        shuffled = r_end is not None
+        if not shuffled:
+            r_end = int(r_begin) + 1
+        R = int(r_end) - int(r_begin)
+
+        def buf(t, shape, name, dt=torch.int64):
+            if t is None:
+                return torch.zeros(shape, dtype=dt, device=dev)
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {tuple(shape)} on {dev}")
+            return t
+        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
+        token_sum = buf(token_sum, (B,), "token_sum")
+        vote_count_sum = buf(vote_count_sum, (B,), "vote_count_sum")
+        truth_count_sum = buf(truth_count_sum, (B,), "truth_count_sum")
+        if per_resample is not None and M is None:
+            M = int(per_resample.shape[2])
+        if M is not None:
+            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        if want_cells or cells is not None:
+            cells = buf(cells, (P, B, 16), "cells", torch.uint8)
+        if want_cells or cell_tokens is not None:
+            cell_tokens = buf(cell_tokens, (P, B), "cell_tokens")
+        self.use_torch_stream()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+        check(self._L.scv_token_budget_prefix_i32(self._ctx, ptr(pool), ptr(tokens), ptr(token_budgets), ptr(truth), P, B, N, p_offset, order,
+                                                  r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, ptr(tie_class_hits),
+                                                  ptr(token_sum), ptr(vote_count_sum), ptr(truth_count_sum), ptr(per_resample), ptr(cells),
+                                                  ptr(cell_tokens)))
+        return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
 
 
 class MultiDeviceEngine:
