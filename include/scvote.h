@@ -117,7 +117,10 @@ int scv_set_tuning(scv_ctx* ctx, int copies, int threads, int wg_per_cu, int unr
  * measured slower in rounds 1-3 is gone from the library (DESIGN_HISTORY.md 4 lists them with their numbers).
  *   "overwrite_counters"  default 0; 1: DEVICE-mode per-budget counters are OVERWRITTEN, not accumulated into (with few long cells the
  *                         streaming kernel's last workgroup does it and the call is one launch, otherwise a memset precedes the launch)
- *   "path"                0 auto | 1 streaming, whole cells | 2 streaming, split-N + merge | 4 register-resident cells | 5 sorted cells
+ *   "path"                0 auto | 1 streaming, whole cells | 2 streaming, split-N + merge | 4 register-resident cells | 5 sorted cells |
+ *                         3 streaming, whole cells, items round-robin over the workgroups.  (0 .. 2: when the items outnumber the workgroups and
+ *                         are at least 2^20 votes long, a device counter hands out each workgroup's items after its first, so that the early
+ *                         finishers take more; 3 is the order before that, for A/B runs)
  *   "sort_n_min" / "sort_n_max"   defaults 8 / 64: cells of that many votes run one lane per cell, the wave's rows staged through LDS
  *                         by LDS-DMA and sorted in registers (rows that are not 16-byte aligned: from 5); "sort_n_max" = 0: off
  *   "reg_n_max"           default 8192 = its maximum: 32 < N <= this uses the register-resident cell kernels; 0: the streaming kernel

@@ -129,7 +129,7 @@ struct scv_ctx {
     int copies = 16, threads = 1024, wg_per_cu = 1, unroll = 4;
     bool user_tuned = false; // set_tuning called: auto geometry off
     // options (scv_set_option; include/scvote.h documents every key)
-    int path = 0;            // 0 auto | 1 streaming, whole cells | 2 streaming, split-N | 4 register-resident cells | 5 sorted cells
+    int path = 0;            // 0 auto | 1 streaming, whole cells | 2 streaming, split-N | 3 streaming, whole cells, round-robin items | 4 register-resident cells | 5 sorted cells
     int segs_override = 0;   // > 0: segments per cell for path 2
     int split_seg_kb = 256;  // split-N: smallest segment the auto choice cuts (KiB)
     int overwrite_counters = 0;  // DEVICE mode: per-budget outputs are overwritten instead of accumulated into (no caller memset)
@@ -259,7 +259,7 @@ int ensure_cells(scv_ctx* ctx, size_t bytes) {
 // Arrival counters of the single-launch modes (overwrite-counters, vote + bootstrap): 4 words, zero when allocated at scv_create,
 // and every counter is reset by the workgroup that completes it, so they are all-zero again whenever no launch is in flight.
 // Nothing allocates on the launch path: legal inside hipGraph capture and independent of later scv_set_stream calls.
-constexpr size_t kTicketWords = 8 + scv::kSplitTickets;     // [0 .. 2] the single-launch epilogues | [8 + cell] split-N arrival counters
+constexpr size_t kTicketWords = 8 + scv::kSplitTickets;     // [0 .. 2] the single-launch epilogues | [3] the dynamic-items dispenser | [8 + cell] split-N arrival counters
 
 // split-N scratch: the split cells' histograms and token sums in memory.  All zero whenever no launch is in flight (the workgroup that
 // finishes a cell clears what it read), so it is cleared here once, when it is (re)allocated -- ON THE CONTEXT'S STREAM: the stream is
@@ -320,7 +320,7 @@ int launch_aggregate(scv_ctx* ctx, const int32_t* answers, const int32_t* tokens
         const bool sort_ok = !pool_rows && ctx->sort_n_max > 0 && N >= (rows_aligned ? 4 : 1) && N <= (ctx->sort_n_max < 64 ? ctx->sort_n_max : 64);
         if (ctx->path == 5) kind = sort_ok ? SORT : (N <= ctx->tiny_n_max ? LANE : (Nreg <= 8192 ? REG : STREAM));
         else if (ctx->path == 4) kind = (Nreg <= 8192 && N >= 1) ? REG : STREAM;
-        else if (ctx->path == 1 || ctx->path == 2) kind = STREAM;
+        else if (ctx->path >= 1 && ctx->path <= 3) kind = STREAM;
         else if (sort_ok && N >= (rows_aligned ? ctx->sort_n_min : (ctx->sort_n_min < 5 ? ctx->sort_n_min : 5))) kind = SORT;
         else if (N <= ctx->tiny_n_max) kind = LANE;
         else if (N <= ctx->reg_n_max && Nreg <= 8192) kind = REG;
@@ -669,6 +669,11 @@ int launch_aggregate(scv_ctx* ctx, const int32_t* answers, const int32_t* tokens
             a.tickets = static_cast<uint32_t*>(ctx->d_tickets);
         }
     }
+    // Dynamic items: the workgroups of a round-robin launch over 4 MiB cells finish up to ~10 % apart (more on some allocations), and the
+    // launch waits for the slowest; a counter that hands out the items lets the early finishers take more (profiles/r06_footprint_probe.log,
+    // r06_dynamic_items_ab.log).  Items of at least 2^20 votes -- the length it was measured at; option path = 3 keeps the round-robin order.
+    if (ctx->path != 3 && nitems > grid && nitems < ((int64_t)1 << 31) && (S > 1 ? a.seg_len : N) >= ((int64_t)1 << 20))
+        a.dispenser = static_cast<uint32_t*>(ctx->d_tickets) + 3;
     const bool xtra = a.overwrite != 0 || a.boot != 0;
     KernelFn fn = pick_kernel(copies, threads, unroll, tok, xtra);
     if (!fn) return fail(SCV_ERR_ARG, "streaming geometry copies=%d threads=%d unroll=%d is not instantiated (scv_set_tuning lists the ones that are)", copies, threads, unroll);
@@ -1246,7 +1251,7 @@ int scv_set_option(scv_ctx* ctx, const char* key, int64_t value) {
             if (value) { ctx->copies = 16; ctx->threads = 1024; ctx->wg_per_cu = 1; ctx->unroll = 4; ctx->user_tuned = false; }
             else ctx->user_tuned = true;
         }
-        else if (!strcmp(key, "path")) { if (value < 0 || value > 5 || value == 3) return fail(SCV_ERR_ARG, "path must be 0, 1, 2, 4 or 5"); ctx->path = (int)value; }
+        else if (!strcmp(key, "path")) { if (value < 0 || value > 5) return fail(SCV_ERR_ARG, "path must be 0 .. 5"); ctx->path = (int)value; }
         else if (!strcmp(key, "sort_n_min")) { if (value < 1 || value > 65) return fail(SCV_ERR_ARG, "sort_n_min must be 1..65"); ctx->sort_n_min = (int)value; }
         else if (!strcmp(key, "sort_n_max")) { if (value < 0 || value > 64) return fail(SCV_ERR_ARG, "sort_n_max must be 0..64"); ctx->sort_n_max = (int)value; }
         else if (!strcmp(key, "reg_n_max")) { if (value < 0) return fail(SCV_ERR_ARG, "reg_n_max < 0"); ctx->reg_n_max = (int)(value > 8192 ? 8192 : value); }
@@ -1510,7 +1515,7 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
     if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
     if ((ctx->flags & SCV_FLAG_PACKED_CELLS) && cells_out) {
         // 4-byte records: DEVICE-mode scv_aggregate_i32 over cells of up to 127 votes (every count fits 7 bits) on the kernels that serve such cells
-        if (prefix || mem_kind != SCV_MEM_DEVICE || N > 127 || ctx->path == 1 || ctx->path == 2 || ctx->fused_counters_max == 0 || ctx->boot_req)
+        if (prefix || mem_kind != SCV_MEM_DEVICE || N > 127 || (ctx->path >= 1 && ctx->path <= 3) || ctx->fused_counters_max == 0 || ctx->boot_req)
             return fail(SCV_ERR_ARG, "SCV_FLAG_PACKED_CELLS: cells_out is uint32 [P, B] only for scv_aggregate_i32 on DEVICE memory with N <= 127 "
                                      "(auto dispatch; no prefix budgets, no bootstrap in the call); got prefix=%d mem_kind=%d N=%lld", (int)prefix, mem_kind, (long long)N);
     }

@@ -94,6 +94,9 @@ struct AggArgs {
     int32_t packed_cells = 0;       // SCV_FLAG_PACKED_CELLS: cells is uint32 [P, B] (cells of up to 127 votes; pack_cell below), not scv_cell [P, B]
     int32_t budgets_promised = 0;   // scv_sort_prefix: != 0 = the budgets are KNOWN to be of its form (read by a HOST-mode call, or promised by the
                                     // caller: option prefix_path = 5): a list that is not sets error bit 8 instead of leaving the launch to another kernel
+    uint32_t* dispenser = nullptr;  // scv_hist_argmax: != NULL = items after each workgroup's first are handed out by this agent-scope counter (ticket t
+                                    // is item gridDim.x + t) instead of round-robin; zero between launches (the workgroup that draws the launch's last
+                                    // ticket, nitems - 1, clears it).  The host sets it only when nitems > gridDim.x.
 };
 
 // SCV_FLAG_PACKED_CELLS (include/scvote.h): one record in 4 bytes -- max_count | truth_count << 7 | n_modes << 14 | min_mode << 21 | hit << 31; every count
@@ -683,10 +686,23 @@ __global__ __launch_bounds__(T) void scv_hist_argmax(const AggArgs a) {
         for (int i = tid; i < kBins * R / 4; i += T) h4[i] = make_uint4(0, 0, 0, 0);
     }
     const bool use_ord = build_budget_order(a, ord, tid, T);
-    __syncthreads();
-
     const int32_t S = a.segs;
     const int64_t nitems = a.ncells * S;
+    // Dynamic items: a static round-robin launch lasts as long as its slowest workgroup, and with the 4 MiB cells of the headline the
+    // workgroups' finish times spread by ~10 % (more on some allocations; profiles/r06_footprint_probe.log).  Thread 0 draws the ticket of
+    // the item AFTER the next one while the next one's first tile is prefetched; the two LDS words alternate, so a ticket is written a whole
+    // item (and barrier B1) before any lane reads it.
+    const bool dyn = a.dispenser != nullptr;
+    uint32_t* dslot = red + 56;                       // red[56 .. 57]
+    uint32_t dpar = 0;
+    auto draw = [&](uint32_t* slot) {
+        const uint32_t t = __hip_atomic_fetch_add(a.dispenser, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *slot = t;
+        if ((int64_t)t + 1 == nitems) st_agent(a.dispenser, 0u);     // the launch's last ticket: every other one has been drawn
+    };
+    if (dyn && tid == 0 && (int64_t)blockIdx.x < nitems) draw(dslot);
+    __syncthreads();
+
     uint32_t bad = 0;
     // Cross-item prefetch (votes-only variant): the first U*T vectors of the NEXT item are loaded into
     // registers before the current item's epilogue (B1 / fold / reductions), so a short cell's load
@@ -726,7 +742,7 @@ __global__ __launch_bounds__(T) void scv_hist_argmax(const AggArgs a) {
             }
         }
     }
-    for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+    for (int64_t item = blockIdx.x, next_item = 0; item < nitems; item = next_item) {
         const int64_t cell = cur.cell, p = cur.p;
         const int32_t b = cur.b;
         long long tsum = 0;
@@ -756,12 +772,15 @@ __global__ __launch_bounds__(T) void scv_hist_argmax(const AggArgs a) {
             const int32_t* trow = TOK ? a.tokens + cell * a.N + cur_lo : nullptr;
             stream_row<RL2, T, U, TOK>(a, hist, copy, cur.row, trow, cur.n, tid, bad, tsum);   // o1.py:181-195
         }
-        const bool more = item + gridDim.x < nitems;
+        next_item = dyn ? (int64_t)gridDim.x + (int64_t)dslot[dpar] : item + gridDim.x;
+        const bool more = next_item < nitems;
+        if (dyn && more && tid == 0) draw(dslot + (dpar ^ 1u));
+        dpar ^= 1u;
         StreamItem nxt = cur;
         int64_t nxt_lo = 0;
         const int4* nxt_t4 = nullptr;
         if (more) {
-            describe_item(a, use_ord, ord, item + gridDim.x, nxt, nxt_lo);
+            describe_item(a, use_ord, ord, next_item, nxt, nxt_lo);
             if (pf) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {

@@ -16,6 +16,9 @@
 //   hbm_probe.bin [cells] --dmawork      ... with the VALU work of a sorted-cells step behind the copy: every wave copying for itself against one
 //                                        producer wave per workgroup (the design question of scv_sort_cells, round 4)
 //   hbm_probe.bin [cells] --vmemq        cycles a wave spends issuing its q-th LDS-DMA piece, back to back: where the memory pipe's queue is full
+//   hbm_probe.bin [cells] --footprint K [--rounds R]   the full-HBM-footprint gap: the headline geometry and one variant per hypothesis
+//                                        (translation: touches ahead, shared cells; workgroup skew: finish stamps, dynamic items) on ONE buffer
+//                                        alone, on each of up to K buffers allocated like bench.py's resident chunks, and in rotation over them
 //   hbm_probe.bin [cells] --calib        3 launches of ONE variant (read_cells_pipe<4>, grid 250 x 1024) and nothing
 //                                        else: run under `rocprofv3 --pmc FETCH_SIZE` to get FETCH_SIZE per launch
 //                                        for exactly cells * 4 MiB of algorithmic reads
@@ -316,6 +319,106 @@ __global__ void vmem_queue(const char* __restrict__ src, int pieces, long wave_s
     }
 }
 
+// ---- the full-HBM-footprint gap (--footprint): one variant per hypothesis, each the baseline read_cells<4, nt> at 250 x 1024 (the
+// geometry and cell order of the headline scv_hist_argmax launch: workgroup b streams cells b, b + 250, ...) changed in ONE respect.
+//
+// H1 (address translation): the workgroup's stream also touches, with ONE plain 4-byte load per 64 KiB step, the word `ahead` vectors
+// further along its own logical stream (into its next cell once past the end of this one), so that the page walk for that address
+// overlaps the stream instead of stalling it.  The touching lane rotates over the 16 waves (step s: wave s % 16), so one wave's wait
+// for a slow translation does not recur every step.
+template <int U>
+__global__ void read_cells_touch(const v4i* __restrict__ src, long cell_vecs, long ncells, long ahead, int* sink) {
+    int acc = 0;
+    const long T = blockDim.x;
+    const long my_cells = blockIdx.x < ncells ? (ncells - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
+    const int nw = (int)(T >> 6), wid = (int)(threadIdx.x >> 6);
+    long step = 0;
+    for (long k = 0; k < my_cells; ++k) {
+        const v4i* p = src + (blockIdx.x + k * gridDim.x) * cell_vecs;
+        for (long i = threadIdx.x; i + (long)(U - 1) * T < cell_vecs; i += (long)U * T, ++step) {
+            v4i x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = ld<true>(p + i + (long)u * T);
+            if ((threadIdx.x & 63) == 0 && wid == (int)(step % nw)) {
+                const long q = (i - threadIdx.x) + ahead;                  // vector offset of the touch in this cell's frame
+                const long kk = k + q / cell_vecs;
+                if (kk < my_cells) acc ^= *(const int*)(src + (blockIdx.x + kk * gridDim.x) * cell_vecs + q % cell_vecs);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc ^= x[u].x ^ x[u].y ^ x[u].z ^ x[u].w;
+        }
+    }
+    if (acc == 0x12345678) *sink = acc;
+}
+
+// H1, second form: G workgroups share each cell (workgroup b is member b % G of group b / G; a group streams cells g, g + grid / G, ...;
+// member m takes the 64 KiB steps m, m + G, ... of each), so only grid / G distinct cells -- and pages -- are in flight at a time.
+template <int U>
+__global__ void read_cells_shared(const v4i* __restrict__ src, long cell_vecs, long ncells, int G, int* sink) {
+    int acc = 0;
+    const long T = blockDim.x;
+    const long ngroups = gridDim.x / G, g = blockIdx.x / G, m = blockIdx.x % G;
+    if (g >= ngroups) return;
+    for (long cell = g; cell < ncells; cell += ngroups) {
+        const v4i* p = src + cell * cell_vecs;
+        for (long i = threadIdx.x + m * U * T; i + (long)(U - 1) * T < cell_vecs; i += (long)G * U * T) {
+            v4i x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = ld<true>(p + i + (long)u * T);
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc ^= x[u].x ^ x[u].y ^ x[u].z ^ x[u].w;
+        }
+    }
+    if (acc == 0x12345678) *sink = acc;
+}
+
+// H2 (workgroup skew and tail): the baseline with a 100 MHz wall-clock stamp per workgroup at its start and after its last step
+// (plain stores by thread 0 into stamps[2 * blockIdx.x + {0, 1}]; the host sizes stamps at 2 x grid).
+template <int U>
+__global__ void read_cells_stamped(const v4i* __restrict__ src, long cell_vecs, long ncells, unsigned long long* stamps, int* sink) {
+    const unsigned long long t0 = wall_clock64();
+    int acc = 0;
+    for (long cell = blockIdx.x; cell < ncells; cell += gridDim.x) {
+        const v4i* p = src + cell * cell_vecs;
+        for (long i = threadIdx.x; i + (long)(U - 1) * blockDim.x < cell_vecs; i += (long)U * blockDim.x) {
+            v4i x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = ld<true>(p + i + (long)u * blockDim.x);
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc ^= x[u].x ^ x[u].y ^ x[u].z ^ x[u].w;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { stamps[2 * blockIdx.x] = t0; stamps[2 * blockIdx.x + 1] = wall_clock64(); }
+    if (acc == 0x12345678) *sink = acc;
+}
+
+// H2 variant: dynamic assignment.  An agent-scope counter (zeroed by a hipMemsetAsync queued in front of every launch) hands out items of
+// `item_vecs` vectors (a whole cell, or half of one) in address order; thread 0 takes the ticket of the NEXT item when the workgroup
+// starts the current one, so the only cost at an item boundary is the barrier that publishes it (double-buffered LDS word).
+template <int U>
+__global__ void read_cells_dynamic(const v4i* __restrict__ src, long item_vecs, long nitems, unsigned* counter, int* sink) {
+    __shared__ long next[2];
+    int acc = 0;
+    if (threadIdx.x == 0) next[0] = (long)atomicAdd(counter, 1u);
+    __syncthreads();
+    for (int k = 0;; k ^= 1) {
+        const long item = next[k];
+        if (item >= nitems) break;
+        if (threadIdx.x == 0) next[k ^ 1] = (long)atomicAdd(counter, 1u);
+        const v4i* p = src + item * item_vecs;
+        for (long i = threadIdx.x; i + (long)(U - 1) * blockDim.x < item_vecs; i += (long)U * blockDim.x) {
+            v4i x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = ld<true>(p + i + (long)u * blockDim.x);
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc ^= x[u].x ^ x[u].y ^ x[u].z ^ x[u].w;
+        }
+        __syncthreads();
+    }
+    if (acc == 0x12345678) *sink = acc;
+}
+
 __global__ void fill(v4i* dst, long nvec) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
@@ -340,9 +443,143 @@ double time_ms(F f, int reps = 5) {
     return t[t.size() / 2];
 }
 
+// --footprint K: does the read rate of the headline geometry follow how much HBM is allocated?  Three phases over buffers of `ncells` x 4 MiB
+// (10000 = one bench chunk, 41.94 GB), each filled once:
+//   alone   ONE buffer, nothing else allocated
+//   full    up to K buffers allocated one after another the way bench.py holds its resident chunks (stop at the first failed hipMalloc or
+//           when the next one would leave less than 3 GiB free); every buffer in turn, then the baseline over the buffers in rotation
+//           (bench.py's step sequence) and the per-workgroup finish times
+//   again   all freed, ONE buffer allocated afresh
+// In each phase and on each buffer, every variant runs `rounds` times, each time right after a run of the baseline (median of 3 launches
+// per run); a variant's line is the median of its runs and its change against the median of the baseline runs in between.
+static int run_footprint(int K, long ncells, long cell_vecs, int rounds) {
+    const long bytes = ncells * cell_vecs * 16;
+    const size_t headroom = 3ull << 30;
+    int* sink; unsigned* counter; unsigned long long* stamps;
+    CK(hipMalloc(&sink, 4)); CK(hipMalloc(&counter, 4)); CK(hipMalloc(&stamps, sizeof(unsigned long long) * 2 * 256));
+    struct V { const char* name; int kind; long arg; };
+    // kind: 0 baseline read_cells<4,nt> 250 x 1024 | 1 read_cells<2,nt> 512 x 512 | 2 read_cells<2,nt> 1000 x 256 | 3 read_cells_pipe<4,nt> 1000 x 256
+    //       4 H1 touch, arg = bytes ahead | 5 H1 shared cells, arg = G | 6 baseline at 256 x 1024 | 7 H2 dynamic, arg = items per cell (grid 256)
+    //       8 H2 dynamic whole cells at 250 x 1024
+    const V vs[] = {{"quick cells U2 nt 512 x 512", 1, 0}, {"quick cells U2 nt 1000 x 256", 2, 0}, {"quick pipe U4 nt 1000 x 256", 3, 0},
+                    {"H1 touch +64 KiB", 4, 64l << 10}, {"H1 touch +256 KiB", 4, 256l << 10}, {"H1 touch +1 MiB", 4, 1l << 20},
+                    {"H1 touch +2 MiB", 4, 2l << 20}, {"H1 touch +4 MiB", 4, 4l << 20}, {"H1 touch +8 MiB", 4, 8l << 20},
+                    {"H1 2 WGs share a cell (125 cells in flight)", 5, 2}, {"H1 4 WGs share a cell, 256 WGs (64 in flight)", 5, 4},
+                    {"H2 static 256 x 1024", 6, 0}, {"H2 dynamic cells 256 x 1024", 7, 1}, {"H2 dynamic half cells 256 x 1024", 7, 2},
+                    {"H2 dynamic cells 250 x 1024", 8, 0}};
+    auto launch = [&](const v4i* b, int kind, long arg) {
+        switch (kind) {
+            case 0: read_cells<4, true><<<250, 1024>>>(b, cell_vecs, ncells, sink); break;
+            case 1: read_cells<2, true><<<512, 512>>>(b, cell_vecs, ncells, sink); break;
+            case 2: read_cells<2, true><<<1000, 256>>>(b, cell_vecs, ncells, sink); break;
+            case 3: read_cells_pipe<4, true><<<1000, 256>>>(b, cell_vecs, ncells, sink); break;
+            case 4: read_cells_touch<4><<<250, 1024>>>(b, cell_vecs, ncells, arg / 16, sink); break;
+            case 5: read_cells_shared<4><<<arg == 4 ? 256 : 250, 1024>>>(b, cell_vecs, ncells, (int)arg, sink); break;
+            case 6: read_cells<4, true><<<256, 1024>>>(b, cell_vecs, ncells, sink); break;
+            case 7: CK(hipMemsetAsync(counter, 0, 4, 0)); read_cells_dynamic<4><<<256, 1024>>>(b, cell_vecs / arg, ncells * arg, counter, sink); break;
+            case 8: CK(hipMemsetAsync(counter, 0, 4, 0)); read_cells_dynamic<4><<<250, 1024>>>(b, cell_vecs, ncells, counter, sink); break;
+        }
+        CK(hipGetLastError());
+    };
+    auto gbps = [&](double ms) { return bytes / ms / 1e6; };
+    auto median = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; };
+    auto stamped = [&](const char* tag, const v4i* b) {
+        read_cells_stamped<4><<<250, 1024>>>(b, cell_vecs, ncells, stamps, sink); CK(hipDeviceSynchronize());
+        read_cells_stamped<4><<<250, 1024>>>(b, cell_vecs, ncells, stamps, sink); CK(hipDeviceSynchronize());
+        std::vector<unsigned long long> s(2 * 250);
+        CK(hipMemcpy(s.data(), stamps, sizeof(unsigned long long) * s.size(), hipMemcpyDeviceToHost));
+        unsigned long long t0 = ~0ull, smax = 0;
+        for (int w = 0; w < 250; ++w) { t0 = std::min(t0, s[2 * w]); smax = std::max(smax, s[2 * w]); }
+        std::vector<double> e(250);
+        for (int w = 0; w < 250; ++w) e[w] = (s[2 * w + 1] - t0) / 100.0;     // 100 MHz -> us
+        std::sort(e.begin(), e.end());
+        printf("%s stamps (us from the first start, 250 workgroups): last start %6.1f | finish min %7.1f p10 %7.1f median %7.1f p90 %7.1f max %7.1f | "
+               "tail (max - median) %5.1f = %4.2f %% of the launch\n", tag, (smax - t0) / 100.0, e[0], e[25], e[125], e[225], e[249],
+               e[249] - e[125], 100.0 * (e[249] - e[125]) / e[249]);
+    };
+    auto sweep = [&](const char* tag, const v4i* b) {
+        const int nv = (int)(sizeof(vs) / sizeof(vs[0]));
+        std::vector<double> base;
+        std::vector<std::vector<double>> t(nv), rel(nv);
+        for (int r = 0; r < rounds; ++r)
+            for (int v = 0; v < nv; ++v) {
+                const double b0 = time_ms([&] { launch(b, 0, 0); }, 3);
+                const double x = time_ms([&] { launch(b, vs[v].kind, vs[v].arg); }, 3);
+                base.push_back(b0); t[v].push_back(x); rel[v].push_back(b0 / x - 1.0);
+            }
+        const double bm = median(base);
+        printf("%s %-46s %7.3f ms %6.0f GB/s  (%zu runs, min %.3f max %.3f ms)\n", tag, "baseline cells U4 nt 250 x 1024", bm, gbps(bm), base.size(),
+               *std::min_element(base.begin(), base.end()), *std::max_element(base.begin(), base.end()));
+        for (int v = 0; v < nv; ++v) {
+            const double m = median(t[v]);
+            printf("%s %-46s %7.3f ms %6.0f GB/s  %+6.2f %% against the baseline run before it (median of %d)\n", tag, vs[v].name, m, gbps(m),
+                   100.0 * median(rel[v]), rounds);
+        }
+        stamped(tag, b);
+        fflush(stdout);
+    };
+    auto alloc_fill = [&](v4i** b) -> bool {
+        size_t fr = 0, tot = 0;
+        CK(hipMemGetInfo(&fr, &tot));
+        if (fr < (size_t)bytes + headroom) return false;
+        if (hipMalloc(b, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        fill<<<4096, 256>>>(*b, bytes / 16); CK(hipGetLastError()); CK(hipDeviceSynchronize());
+        return true;
+    };
+    auto meminfo = [&](const char* when) {
+        size_t fr = 0, tot = 0;
+        CK(hipMemGetInfo(&fr, &tot));
+        printf("memory %-28s free %7.2f GB of %7.2f GB\n", when, fr / 1e9, tot / 1e9);
+    };
+    printf("footprint: buffers of %ld cells x 4 MiB = %.3f GB; %d rounds per variant\n", ncells, bytes / 1e9, rounds);
+    meminfo("at start");
+    v4i* one;
+    if (!alloc_fill(&one)) { printf("footprint: not even one buffer fits\n"); return 1; }
+    sweep("alone  ", one);
+    CK(hipFree(one));
+    std::vector<v4i*> bufs;
+    for (int k = 0; k < K; ++k) {
+        v4i* b;
+        if (!alloc_fill(&b)) break;
+        bufs.push_back(b);
+    }
+    printf("footprint: %zu of %d buffers allocated (%.1f GB)\n", bufs.size(), K, bufs.size() * bytes / 1e9);
+    for (size_t k = 0; k < bufs.size(); ++k) printf("buffer %zu at %p\n", k, (void*)bufs[k]);
+    meminfo("with every buffer allocated");
+    for (size_t k = 0; k < bufs.size(); ++k) {
+        char tag[32];
+        snprintf(tag, sizeof tag, "full %zu/%zu", k, bufs.size());
+        sweep(tag, bufs[k]);
+    }
+    {   // the baseline over the buffers in rotation, one launch per buffer (bench.py's step sequence), per-launch events
+        const int n = (int)bufs.size(), reps = 8;
+        hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        std::vector<std::vector<double>> per(n);
+        for (int i = 0; i < n * (reps + 1); ++i) {
+            CK(hipEventRecord(e0)); launch(bufs[i % n], 0, 0); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (i >= n) per[i % n].push_back(ms);
+        }
+        std::vector<double> all;
+        for (int k = 0; k < n; ++k) {
+            printf("rotation buffer %d: median %.3f ms = %6.0f GB/s (min %.3f max %.3f, %d launches)\n", k, median(per[k]), gbps(median(per[k])),
+                   *std::min_element(per[k].begin(), per[k].end()), *std::max_element(per[k].begin(), per[k].end()), reps);
+            all.insert(all.end(), per[k].begin(), per[k].end());
+        }
+        printf("rotation all: median %.3f ms = %6.0f GB/s\n", median(all), gbps(median(all)));
+    }
+    for (v4i* b : bufs) CK(hipFree(b));
+    meminfo("after freeing them");
+    if (!alloc_fill(&one)) { printf("footprint: one buffer no longer fits\n"); return 1; }
+    sweep("again  ", one);
+    CK(hipFree(one));
+    return 0;
+}
+
 int main(int argc, char** argv) {
     long ncells = 10000;
     bool calib = false, shortcells = false, quick = false, percu = false, dma = false, c2 = false, dmawork = false, vmemq = false;
+    int footprint = 0, rounds = 3;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--calib")) calib = true;
         else if (!strcmp(argv[i], "--short")) shortcells = true;
@@ -352,10 +589,13 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--dmawork")) dmawork = true;
         else if (!strcmp(argv[i], "--vmemq")) vmemq = true;
         else if (!strcmp(argv[i], "--c2")) c2 = true;
+        else if (!strcmp(argv[i], "--footprint") && i + 1 < argc) footprint = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--rounds") && i + 1 < argc) rounds = atoi(argv[++i]);
         else ncells = atol(argv[i]);
     }
     const long cell_bytes = 4l << 20;
     const long bytes = ncells * cell_bytes, nvec = bytes / 16, cell_vecs = cell_bytes / 16;
+    if (footprint > 0) return run_footprint(footprint, ncells, cell_vecs, rounds);
     v4i* buf; int* sink;
     CK(hipMalloc(&buf, bytes)); CK(hipMalloc(&sink, 4));
     fill<<<4096, 256>>>(buf, nvec); CK(hipDeviceSynchronize());
