@@ -337,6 +337,51 @@ int scv_token_budget_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t
                                 int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out);
 
 /*
+ * Weighted majority vote and best-of-N over the prefixes of a pool ordering (new semantics, not in the reference, whose every rule counts a
+ * sample once: statistics.multimode, o1.py:202-213).  Each sample votes with an integer weight -- a verifier or reward-model score, a
+ * confidence, quantised by the caller (o1_inference_scaling_laws_amd/weighted.py: quantize_weights).
+ *   pool int32 [P, N]; weights int32 [P, N] (required), each in 0 .. SCV_WEIGHT_MAX = 2^24 - 1; tokens int32 [P, N] (NULL ok);
+ *   n_valid int32 [B] (required, any order, duplicates fine); truth int32 [P]
+ * For problem p (global index pg = p_offset + p), an ordering pi and budget k_b = clamp(n_valid[b], 0, N), over the samples pi(0 : k_b):
+ *   W(v)   = the SUM of the weights of the samples whose vote is v          rule SCV_RULE_WEIGHT_SUM (0): weighted majority vote
+ *          = the MAXIMUM of those weights                                    rule SCV_RULE_BEST_OF (1): the answer of the best-scored sample
+ *   modes  = the values with W(v) == max_v W(v) > 0.  A value of weight 0 is never a mode; an empty prefix, or one whose weights are all 0,
+ *            has no mode and no hit (max_count 0, n_modes 0, min_mode -1), like the empty cell everywhere else
+ *   score  = 1 / n_modes if the truth is a mode, else 0 (as everywhere: tie_class_hits, per_resample and scoring.py are used unchanged).
+ *            Under rule 1 a tie for the top weight between samples of different votes is a tie between those votes
+ *   order  SCV_ORDER_POOL (0): pi is the identity, the cache order (one draw): r_begin = 0, r_end = 1 required
+ *          SCV_ORDER_SHUFFLED (1): pi is EXACTLY the partial Fisher-Yates permutation of scv_resample_prefix_i32 for (seed, pg, r),
+ *          r in [r_begin, r_end)
+ * With every weight 1 and rule 0 the call is the plain vote of scv_resample_prefix_i32 / scv_aggregate_prefix_i32.  With N <= 256 every W
+ * is below 2^32: all sums are exact.  A weight outside 0 .. SCV_WEIGHT_MAX sets error bit 5: SCV_ERR_ARG at the call in HOST mode, at
+ * scv_sync in DEVICE mode.  Votes and truths follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN) or
+ * counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
+ *   token_sum_out        int64 [B]        (NULL ok; requires tokens) tokens of the samples in the prefixes
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) class counts per ordering, summed over problems only (m < M; a hit with
+ *                        n_modes >= M sets error bit 1: SCV_ERR_ARG at scv_sync)
+ *   cells_out            scv_cell [P, B] (NULL ok; SCV_ORDER_POOL only): the cells of the cache order.  Here max_count and truth_count
+ *                        carry WEIGHTS: max_count = the top W, truth_count = W(truth); n_modes, min_mode and hit as always
+ *   cell_tokens_out      int64 [P, B] (NULL ok; SCV_ORDER_POOL only; requires tokens).  Both cell outputs are OVERWRITTEN in both modes
+ * DEVICE mode ACCUMULATES into the per-budget outputs and per_resample (+=) and only enqueues: no allocation, no synchronisation, legal
+ * under hipGraph capture.  HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices of r and shards of p
+ * (p_offset) add up to the whole call bit for bit.  Limits: 1 <= N <= 256, 1 <= B <= 32, 0 <= r_begin <= r_end, p_offset >= 0, M >= 1
+ * when per_resample_out is given; anything else -- a bad rule or order, NULL weights, SCV_ORDER_POOL with an r-range other than [0, 1), cell
+ * outputs with SCV_ORDER_SHUFFLED -- is SCV_ERR_ARG.  One lane per (problem, ordering), one launch per DEVICE call
+ * (csrc/scvote_weighted.hip.h).
+ */
+#define SCV_RULE_WEIGHT_SUM 0
+#define SCV_RULE_BEST_OF 1
+#define SCV_WEIGHT_MAX 16777215   /* 2^24 - 1 */
+int scv_weighted_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* weights, const int32_t* tokens,
+                            const int32_t* n_valid, const int32_t* truth,
+                            int64_t P, int32_t B, int64_t N, int64_t p_offset, int rule, int order,
+                            int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                            int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* per_resample_out,
+                            scv_cell* cells_out, int64_t* cell_tokens_out);
+
+/*
  * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
  * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
  * seed and nothing left to converge.
@@ -365,7 +410,7 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
 
 /*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the

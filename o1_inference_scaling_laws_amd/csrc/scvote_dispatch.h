@@ -86,9 +86,13 @@ struct ResampleArgs {
     int32_t order;                                       // kOrderPool (x = i, R = 1) | kOrderShuffled (the shuffle above)
     unsigned long long* vote_sum;                        // [B] votes in the prefixes (NULL ok)
     scv_cell* cells_out; int64_t* cell_tokens_out;       // [P, B] (NULL ok; pool order only), overwritten
+    // appended for the weighted vote (scv_weighted_prefix_i32, scvote_weighted.hip.h): n_valid holds the budgets, tokens may be NULL
+    const int32_t* weights;                              // [P, N] in 0 .. SCV_WEIGHT_MAX
+    int32_t rule;                                        // 0: W(v) = sum of the weights (SCV_RULE_WEIGHT_SUM) | 1: their maximum (SCV_RULE_BEST_OF)
+    int32_t wlds;                                        // rows staged in LDS as code | weight << 8 words (weighted_rows_in_lds)
 };
 using ResampleFn = void (*)(const ResampleArgs);
-constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2;
+constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3;
 constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
 // LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
 // budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
@@ -96,6 +100,18 @@ constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV
 constexpr long long token_budget_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
     return 64 + 6LL * B + 32 + (long long)B * (N + 1) + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) +
            (shuffled ? 2LL : 1LL) * lanes * ((N + 3) / 4);
+}
+// The weighted body stages a row as N words (code | weight << 8) when a chunk of lanes touches few rows, R >= kWeightedLdsRowsMinR (at most
+// lanes / R + 2 rows); below that -- and in pool order, R = 1 -- as byte codes, with the weight read from global memory: lanes + 1 rows of N words
+// would not fit beside the lanes' totals.
+constexpr int kWeightedLdsRowsMinR = 64;
+constexpr bool weighted_rows_in_lds(long long R, bool shuffled) { return shuffled && R >= kWeightedLdsRowsMinR; }
+// LDS words of a weighted-vote workgroup (scvote_weighted.hip.h, in this order): per-budget token sums (B int64) | tie classes [B][N + 1] |
+// sorted budgets and their order (2 x 32) | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] | the rows
+// [np_max][N words or N4 words of byte codes] | the lanes' uint32 totals [N][lanes] | their Fisher-Yates arrays [N4][lanes] (shuffled order only)
+constexpr long long weighted_lds_words(int N, int B, int lanes, int np_max, bool shuffled, bool wlds) {
+    return 2LL * B + (long long)B * (N + 1) + 64 + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * (wlds ? N : (N + 3) / 4) +
+           (long long)lanes * N + (shuffled ? (long long)lanes * ((N + 3) / 4) : 0LL);
 }
 // the context's table (kExpectedTabWords doubles: binomials | Gauss-Legendre rules) and its layout: scvote_expected_table.h
 constexpr int kExpectedLanes = 256;

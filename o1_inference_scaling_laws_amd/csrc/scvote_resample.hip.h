@@ -29,8 +29,9 @@
 //    no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
 //
 // LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
-// The <false> instantiation has a second body, the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h);
-// the <true> one the vote over the longest prefix that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h).
+// The <false> instantiation has two more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h)
+// and the weighted vote / best-of-N (mode kResampleModeWeighted, scvote_weighted.hip.h); the <true> one the vote over the longest prefix
+// that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h).
 #pragma once
 
 #include "scvote_kernels.hip.h"
@@ -103,6 +104,7 @@ __device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64
 
 #include "scvote_expected.hip.h"
 #include "scvote_budget.hip.h"
+#include "scvote_weighted.hip.h"
 
 namespace scv {
 
@@ -111,6 +113,7 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
     extern __shared__ __attribute__((aligned(16))) uint32_t smem_wg[];
     if constexpr (!TOK) {
         if (a.mode == kResampleModeExpected) { expected_majority_body(a, smem_wg); return; }    // the exact form: scvote_expected.hip.h
+        if (a.mode == kResampleModeWeighted) { weighted_body(a, smem_wg); return; }             // weighted vote / best-of-N: scvote_weighted.hip.h
     } else {
         if (a.mode == kResampleModeTokenBudget) { token_budget_body(a, smem_wg); return; }      // token budgets: scvote_budget.hip.h
     }

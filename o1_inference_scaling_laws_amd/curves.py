@@ -68,3 +68,20 @@ def token_budget_records(engine, pool, truth, tokens, token_limits, resamples: i
                                      np.array(limits, dtype=np.int64), resamples=resamples, seed=seed, M=0)
     return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
             for b, t in enumerate(limits)]
+
+
+def weighted_majority_records(engine, pool, weights, truth, tokens, token_limits, rule, resamples: int | None = None, seed: int = 0):
+    """pool / weights / tokens int32 [P, Npool] (the 2^11-token samples of each problem in cache order, each with an integer weight in
+    0 .. WEIGHT_MAX: weighted.quantize_weights), truth int32 [P].  For every token limit T >= 2^11 (the budgets of resampled_budgets,
+    N = T // 2^11 samples): the accuracy of the weighted majority vote (``rule`` RULE_WEIGHT_SUM) or of best-of-N (RULE_BEST_OF) over the
+    first N samples -- of the cache order (``resamples=None``, one draw) or averaged over ``resamples`` random orderings -- and the tokens
+    used (Engine.weighted_prefix, scv_weighted_prefix_i32), as records {'token_limit', 'accuracy', 'avg_tokens_used'} (o1.py:278-283):
+    the curve drops into plot_helpers next to the plain vote's.  ``tokens`` may be None (avg_tokens_used is then 0.0)."""
+    budgets = resampled_budgets(token_limits)
+    pool = np.asarray(pool, dtype=np.int32)
+    ns = np.array([n for _t, n in budgets], dtype=np.int32)
+    if len(ns) and ns.max() > pool.shape[1]:
+        raise ValueError(f"token limit {budgets[int(ns.argmax())][0]} needs {int(ns.max())} samples per problem; the pool has {pool.shape[1]}")
+    res = engine.weighted_prefix(pool, weights, truth, ns, rule=rule, resamples=resamples, seed=seed, M=0, tokens=tokens)
+    return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
+            for b, (t, _n) in enumerate(budgets)]

@@ -21,6 +21,7 @@ from ._lib import TIE_CLASSES, check
 from .expected import ExpectedResult
 from .resample import ResampleResult
 from .token_budget import TokenBudgetResult
+from .weighted import WeightedResult
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
 CELL_DTYPE = np.dtype(
@@ -354,6 +355,48 @@ class Engine:
                                                   _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
         return TokenBudgetResult(P, R, tie, tok, votes, tcs, per, cells, cell_tokens)
 
+    def weighted_prefix(self, pool, weights, truth, n_valid, rule: int = _lib.RULE_WEIGHT_SUM, resamples: int | None = None, seed: int = 0,
+                        r_begin: int = 0, p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False) -> WeightedResult:
+        """Weighted majority vote (``rule`` RULE_WEIGHT_SUM) or best-of-N (RULE_BEST_OF) over the first n_valid[b] samples of each pool
+        ordering (scv_weighted_prefix_i32; CPU mirror: weighted.py).  pool / weights int32 [P, N] (numpy, N <= 256, weights in
+        0 .. WEIGHT_MAX: weighted.quantize_weights), truth [P], n_valid int32 [B] (B <= 32, any order), tokens [P, N] or None.
+        ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells, whose max_count / truth_count carry weights);
+        otherwise the orderings r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of ``per_resample`` (None: N + 1,
+        which no hit can exceed; 0: not computed).  Blocking."""
+        pool = np.ascontiguousarray(pool, dtype=np.int32)
+        if pool.ndim != 2:
+            raise ValueError("pool must be [P, N]")
+        P, N = pool.shape
+        if weights is None:
+            raise ValueError("weights are required")
+        weights = np.ascontiguousarray(weights, dtype=np.int32)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
+        if weights.shape != pool.shape or truth.shape != (P,) or n_valid.ndim != 1:
+            raise ValueError("weights must match pool, truth must be [P] and n_valid [B]")
+        B = n_valid.shape[0]
+        if tokens is not None:
+            tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+            if tokens.shape != pool.shape:
+                raise ValueError("tokens must match pool")
+        shuffled = resamples is not None
+        if want_cells and shuffled:
+            raise ValueError("cells are written in pool order only (resamples=None)")
+        r0, r1 = (int(r_begin), int(r_begin) + int(resamples)) if shuffled else (int(r_begin), int(r_begin) + 1)
+        R = r1 - r0
+        if M is None:
+            M = N + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64) if tokens is not None else None
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
+        cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells and tokens is not None else None
+        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+        check(self._L.scv_weighted_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(weights), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth),
+                                              P, B, N, p_offset, int(rule), order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
+                                              _np_ptr(tok), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
+        return WeightedResult(P, R, tie, tok, per, cells, cell_tokens)
+
     # ---- DEVICE mode (torch tensors; asynchronous on torch's current stream) --------------------
 
     def _device_call(self, votes, votes_name, row_shape, truth, tokens, n_valid, counters, cells, cell_tokens, overwrite, want_no_cells=True):
@@ -600,6 +643,58 @@ class Engine:
                                                   ptr(token_sum), ptr(vote_count_sum), ptr(truth_count_sum), ptr(per_resample), ptr(cells),
                                                   ptr(cell_tokens)))
         return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
+
+    def weighted_prefix_device(self, pool, weights, truth, n_valid, rule: int = _lib.RULE_WEIGHT_SUM, r_begin: int = 0, r_end: int | None = None,
+                               seed: int = 0, p_offset: int = 0, tokens=None, tie_class_hits=None, token_sum=None, per_resample=None,
+                               M: int | None = None, cells=None, cell_tokens=None, want_cells: bool = False):
+        """DEVICE-mode weighted_prefix: pool / weights (/ tokens) torch.int32 cuda [P, N], truth [P], n_valid [B].  ``r_end=None``: the pool's
+        own order (r_begin must be 0); otherwise the orderings [r_begin, r_end).  ACCUMULATES into the given int64 buffers (tie_class_hits
+        [B, 1025], token_sum [B] -- with tokens --, per_resample [r_end - r_begin, B, M]; those left None are allocated zeroed -- per_resample
+        only when ``M`` is given).  Pool order only: OVERWRITES cells (uint8 [P, B, 16]) and cell_tokens (int64 [P, B], with tokens),
+        allocated when ``want_cells``.  One launch on torch's current stream, does not synchronise (a weight out of range is reported by
+        ``sync``).  Returns (tie_class_hits, token_sum, per_resample, cells, cell_tokens)."""
+        import torch
+        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
+            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
+        self._check_device(pool, "pool")
+        P, N = int(pool.shape[0]), int(pool.shape[1])
+        dev = pool.device
+        if weights is None:
+            raise ValueError("weights are required")
+        B = int(n_valid.shape[0])
+        for name, t, shape in (("weights", weights, (P, N)), ("tokens", tokens, (P, N)), ("truth", truth, (P,)), ("n_valid", n_valid, (B,))):
+            if t is None and name == "tokens":
+                continue
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
+        shuffled = r_end is not None
+        if not shuffled:
+            r_end = int(r_begin) + 1
+        R = int(r_end) - int(r_begin)
+
+        def buf(t, shape, name, dt=torch.int64):
+            if t is None:
+                return torch.zeros(shape, dtype=dt, device=dev)
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {tuple(shape)} on {dev}")
+            return t
+        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
+        token_sum = buf(token_sum, (B,), "token_sum") if tokens is not None else None
+        if per_resample is not None and M is None:
+            M = int(per_resample.shape[2])
+        if M is not None:
+            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        if want_cells or cells is not None:
+            cells = buf(cells, (P, B, 16), "cells", torch.uint8)
+        if (want_cells and tokens is not None) or cell_tokens is not None:
+            cell_tokens = buf(cell_tokens, (P, B), "cell_tokens")
+        self.use_torch_stream()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+        check(self._L.scv_weighted_prefix_i32(self._ctx, ptr(pool), ptr(weights), ptr(tokens), ptr(n_valid), ptr(truth), P, B, N, p_offset,
+                                              int(rule), order, r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE,
+                                              ptr(tie_class_hits), ptr(token_sum), ptr(per_resample), ptr(cells), ptr(cell_tokens)))
+        return tie_class_hits, token_sum, per_resample, cells, cell_tokens
 
 
 class MultiDeviceEngine:

@@ -1,0 +1,173 @@
+"""CPU mirror (numpy) of scv_weighted_prefix_i32, spec in include/scvote.h: the weighted majority vote (rule 0: a value's weight is the sum
+of its samples' weights) and best-of-N (rule 1: the maximum) over the prefixes of a pool ordering.  The orderings are those of
+token_budget.orderings / resample.py (one definition of the shuffle).  Every prefix's W(v) is built from scratch with np.add.at /
+np.maximum.at over the prefix's samples, not by the kernel's running rule, so the two arrive at the modes by different roads.  The
+executable statement of the header text, and what the tests hold the HIP kernel to."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes
+from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
+from .token_budget import orderings
+
+RULE_WEIGHT_SUM, RULE_BEST_OF = 0, 1
+WEIGHT_MAX = 2 ** 24 - 1
+ERR_WEIGHT_BIT = 32                             # bit 5 of the device error word: a weight outside 0 .. WEIGHT_MAX
+LANE_BLOCK = 4096                               # lanes per block of the mirror (bounds its [lanes, N] tables)
+
+
+@dataclass
+class WeightedResult:
+    """Integer outputs of one weighted-vote call + the floats derived from them.  Every denominator is P * R (cells per budget; R = 1 in
+    pool order): accuracy(b) is the weighted vote (or best-of-N) over k_b samples averaged over problems (and orderings)."""
+    P: int
+    R: int
+    tie_class_hits: np.ndarray          # int64 [B, 1025]
+    token_sum: np.ndarray | None        # int64 [B]: tokens of the samples in the prefixes (None without tokens)
+    per_resample: np.ndarray | None     # int64 [R, B, M]
+    cells: np.ndarray | None = None     # CELL_DTYPE [P, B] (pool order): max_count = the top weight, truth_count = the truth's weight
+    cell_tokens: np.ndarray | None = None   # int64 [P, B] (pool order, with tokens)
+    error_bits: int = 0                 # bit 0: a vote outside 0..1023; bit 1: a hit with n_modes >= M; bit 5: a weight out of range
+
+    def _den(self):
+        return self.P * self.R
+
+    def accuracy(self, b: int = 0) -> float:
+        return accuracy_from_tie_classes(self.tie_class_hits[b], self._den())
+
+    def exact_accuracy(self, b: int = 0):
+        return exact_accuracy_from_tie_classes(self.tie_class_hits[b], self._den())
+
+    def avg_tokens_used(self, b: int = 0) -> np.float64:
+        return avg_tokens_used(0 if self.token_sum is None else self.token_sum[b], self._den())
+
+    def resample_accuracy(self, b: int = 0) -> np.ndarray:
+        """accuracy of every single ordering r: float64 [R]."""
+        if self.per_resample is None:
+            raise ValueError("per_resample was not requested")
+        m = np.arange(1, self.per_resample.shape[2], dtype=np.float64)
+        return (self.per_resample[:, b, 1:] / m).sum(axis=1) / self.P
+
+
+def quantize_weights(scores, lo=None, hi=None) -> np.ndarray:
+    """Float scores -> int32 weights in 0 .. WEIGHT_MAX: w = floor((clip(s, lo, hi) - lo) / (hi - lo) * WEIGHT_MAX + 0.5) in float64 (round
+    half up), so lo -> 0, hi -> WEIGHT_MAX and s1 <= s2 gives w1 <= w2.  ``lo`` / ``hi`` default to the smallest / largest score; when they
+    coincide every weight is WEIGHT_MAX (all samples vote alike).  NaN is refused.  Scores closer than (hi - lo) / 2^24 may share a weight:
+    a tie the exact scores would not have had."""
+    s = np.asarray(scores, dtype=np.float64)
+    if np.isnan(s).any():
+        raise ValueError("scores contain NaN")
+    lo = (float(s.min()) if s.size else 0.0) if lo is None else float(lo)
+    hi = (float(s.max()) if s.size else 0.0) if hi is None else float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or hi < lo:
+        raise ValueError(f"bad range lo={lo} hi={hi}")
+    if hi == lo:
+        return np.full(s.shape, WEIGHT_MAX, dtype=np.int32)
+    u = (np.clip(s, lo, hi) - lo) / (hi - lo)
+    return np.floor(u * WEIGHT_MAX + 0.5).astype(np.int32)
+
+
+def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
+                    p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False) -> WeightedResult:
+    """pool / weights int32 [P, N], truth [P], n_valid int32 [B].  ``r_end=None``: pool order (one draw, r_begin must be 0); otherwise the
+    shuffled orderings r in [r_begin, r_end).  ``M``: per_resample classes (None: not computed).  ``want_cells``: pool order only."""
+    pool = np.asarray(pool)
+    if pool.ndim != 2:
+        raise ValueError("pool must be [P, N]")
+    P, N = pool.shape
+    if weights is None:
+        raise ValueError("weights are required")
+    wts = np.asarray(weights, dtype=np.int64)
+    truth = np.asarray(truth, dtype=np.int64)
+    nv = np.asarray(n_valid, dtype=np.int64).reshape(-1)
+    B = nv.shape[0]
+    tok = None if tokens is None else np.asarray(tokens, dtype=np.int64)
+    shuffled = r_end is not None
+    if not shuffled:
+        if r_begin != 0:
+            raise ValueError("pool order is one draw: r_begin must be 0")
+        r_end = 1
+    if rule not in (RULE_WEIGHT_SUM, RULE_BEST_OF):
+        raise ValueError(f"bad rule {rule}")
+    if not (1 <= N <= MAX_N and 1 <= B <= MAX_B and 0 <= r_begin <= r_end < 2 ** 31 and p_offset >= 0) or truth.shape != (P,) \
+            or wts.shape != pool.shape or (tok is not None and tok.shape != pool.shape):
+        raise ValueError(f"bad shape P={P} N={N} B={B} r=[{r_begin},{r_end})")
+    if want_cells and shuffled:
+        raise ValueError("cells are written in pool order only")
+    if M is not None and M < 1:
+        raise ValueError("M must be >= 1")
+    R = r_end - r_begin
+    ks = np.clip(nv, 0, N)
+    tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+    tsum = np.zeros(B, dtype=np.int64) if tok is not None else None
+    per = np.zeros((R, B, M), dtype=np.int64) if M is not None else None
+    cells = cell_tokens = None
+    if want_cells:
+        from .engine import CELL_DTYPE
+        cells = np.zeros((P, B), dtype=CELL_DTYPE)
+        cells["min_mode"] = -1
+        cell_tokens = np.zeros((P, B), dtype=np.int64) if tok is not None else None
+    codes, uniq, bad = dense_codes(pool)
+    wbad = (wts < 0) | (wts > WEIGHT_MAX)
+    err = (ERR_DOMAIN_BIT if bad else 0) | (ERR_WEIGHT_BIT if wbad.any() else 0)
+    wts = wts & WEIGHT_MAX                                              # what the kernel counts after it raised the bit (results are invalid)
+    L = P * R
+    if L == 0:
+        return WeightedResult(P, R, tie, tsum, per, cells, cell_tokens, err)
+    tcode = np.full(P, -1, dtype=np.int64)
+    for p in range(P):
+        t = int(truth[p])
+        if 0 <= t < NUM_BINS:
+            k = np.searchsorted(uniq[p], t)
+            if k < len(uniq[p]) and uniq[p][k] == t:
+                tcode[p] = k
+    for l0 in range(0, L, LANE_BLOCK):
+        l1 = min(L, l0 + LANE_BLOCK)
+        lanes = np.arange(l0, l1)
+        lp = lanes // R
+        lr = lanes % R                                                  # relative to r_begin
+        Lb = l1 - l0
+        if shuffled:
+            p_lo, p_hi = int(lp[0]), int(lp[-1]) + 1
+            perm = orderings(p_hi - p_lo, N, r_begin, r_end, seed, p_offset + p_lo)[(lanes - p_lo * R)]
+        else:
+            perm = np.tile(np.arange(N, dtype=np.int64), (Lb, 1))
+        x_codes = codes[lp[:, None], perm]
+        x_w = wts[lp[:, None], perm]
+        x_tok = None if tok is None else tok[lp[:, None], perm]
+        rows = np.arange(Lb)
+        tc_lane = tcode[lp]
+        for b in range(B):
+            k = int(ks[b])
+            W = np.zeros((Lb, N), dtype=np.int64)                        # by row code, from scratch for this prefix
+            if k:
+                idx = (np.repeat(rows, k), x_codes[:, :k].reshape(-1))
+                (np.add if rule == RULE_WEIGHT_SUM else np.maximum).at(W, idx, x_w[:, :k].reshape(-1))
+            top = W.max(axis=1)
+            is_mode = (W == top[:, None]) & (top[:, None] > 0)
+            nm = is_mode.sum(axis=1)
+            tw = np.where(tc_lane >= 0, W[rows, np.maximum(tc_lane, 0)], 0)
+            hit = (tw > 0) & (tw == top)
+            tie[b] += np.bincount(nm[hit], minlength=TIE_CLASSES)[:TIE_CLASSES]
+            spent = None if x_tok is None else x_tok[:, :k].sum(axis=1)
+            if tsum is not None:
+                tsum[b] += int(spent.sum())
+            if per is not None:
+                m = nm[hit]
+                if (m >= M).any():
+                    err |= ERR_CLASS_BIT
+                keep = m < M
+                per[:, b, :] += np.bincount(lr[hit][keep] * M + m[keep], minlength=R * M).reshape(R, M)
+            if cells is not None:
+                mc = np.where(top > 0, is_mode.argmax(axis=1), -1)       # the smallest modal code: codes are value-ordered
+                cells["max_count"][lp, b] = top
+                cells["truth_count"][lp, b] = tw
+                cells["n_modes"][lp, b] = nm
+                cells["min_mode"][lp, b] = [int(uniq[p][c]) if c >= 0 else -1 for p, c in zip(lp.tolist(), mc.tolist())]
+                cells["hit"][lp, b] = hit
+                if cell_tokens is not None:
+                    cell_tokens[lp, b] = spent
+    return WeightedResult(P, R, tie, tsum, per, cells, cell_tokens, err)
