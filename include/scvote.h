@@ -382,6 +382,59 @@ int scv_weighted_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* we
                             scv_cell* cells_out, int64_t* cell_tokens_out);
 
 /*
+ * Adaptive (early-stopping) majority vote: sample until the vote is settled, then stop (new semantics, not in the reference, which fixes
+ * the number of samples in advance; Adaptive-Consistency and early-stopping self-consistency are such policies).  One call scores B stopping
+ * rules on the prefixes of each pool ordering and returns, per rule, the accuracy counters and what the rule spent.
+ *   pool int32 [P, N]; tokens int32 [P, N] (NULL ok; they decide nothing, so a negative count is not an error); truth int32 [P]
+ *   cap int32 [B] (required): n_max_b = clamp(cap[b], 0, N), the most samples rule b may draw
+ *   need int32 [B, N + 1] (required): the stopping table, each value clamped to 0 .. N + 1 on the device
+ *   rule_flags int32 [B] (NULL: all 0): bit 0 SCV_STOP_DECIDED; any other bit is SCV_ERR_ARG (at the call in HOST mode; error bit 6,
+ *   at scv_sync, in DEVICE mode)
+ * For problem p (global index pg = p_offset + p), an ordering pi and rule b the samples pool[p, pi(0)], pool[p, pi(1)], ... are counted one
+ * at a time.  After the n-th sample, 1 <= n <= n_max_b:
+ *   c1 = the largest count of any value
+ *   c2 = the count of the second value in descending order of count: c1 when two or more values tie for the top, 0 when only one distinct
+ *        value has been seen
+ * and the vote stops at the first n for which one of these holds:
+ *   (a) c1 >= need[b][c2]
+ *   (b) SCV_STOP_DECIDED is set and c1 - c2 > n_max_b - n: the unique mode can no longer be caught or tied before the cap
+ *   (c) n == n_max_b
+ * n_max_b == 0 gives the empty cell: no hit, 0 votes, 0 tokens (it stopped after 0 samples).
+ *   cell (p, pi, b) = statistics.multimode over the n samples counted, scored as everywhere (1 / n_modes on a hit)
+ *   order  SCV_ORDER_POOL (0): pi is the identity, the cache order (one draw): r_begin = 0, r_end = 1 required
+ *          SCV_ORDER_SHUFFLED (1): pi is EXACTLY the partial Fisher-Yates permutation of scv_resample_prefix_i32 for (seed, pg, r),
+ *          r in [r_begin, r_end)
+ * need[b][c2] = N + 1 never stops by (a) (with flag 0 the rule is the fixed vote over n_max_b samples); need[b][c2] = c2 + m stops at a lead
+ * of m; o1_inference_scaling_laws_amd/adaptive.py builds these and the Beta criterion of Adaptive-Consistency.  Votes and truths follow
+ * scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at scv_sync in DEVICE mode) or
+ * counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a rule:
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
+ *   token_sum_out        int64 [B]        (NULL ok; requires tokens) tokens of the samples drawn
+ *   vote_count_sum_out   int64 [B]        (NULL ok) the samples drawn
+ *   truth_count_sum_out  int64 [B]        (NULL ok) votes equal to the truth among them
+ *   stop_hist_out        int64 [B, N + 1] (NULL ok) cells that stopped after exactly n samples: the cost distribution of the rule
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) class counts per ordering, summed over problems only (m < M; a hit with
+ *                        n_modes >= M sets error bit 1: SCV_ERR_ARG at scv_sync)
+ *   cells_out            scv_cell [P, B], cell_tokens_out int64 [P, B] (requires tokens), cell_votes_out int32 [P, B] (each NULL ok;
+ *                        SCV_ORDER_POOL only): the cells of the cache order, their tokens and the samples they drew; OVERWRITTEN in both modes
+ * DEVICE mode ACCUMULATES into every other output (+=) and only enqueues: no allocation, no synchronisation, legal under hipGraph capture.
+ * HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices of r and shards of p (p_offset) add up to the
+ * whole call bit for bit.  Limits: 1 <= N <= 256, 1 <= B <= 32, 0 <= r_begin <= r_end, p_offset >= 0, M >= 1 when per_resample_out is
+ * given; anything else -- a bad order, NULL cap or need, SCV_ORDER_POOL with an r-range other than [0, 1), cell outputs with
+ * SCV_ORDER_SHUFFLED, token outputs without tokens -- is SCV_ERR_ARG.  One lane per (problem, ordering) walks until its last rule has
+ * stopped, one launch per DEVICE call (csrc/scvote_adaptive.hip.h).
+ */
+#define SCV_STOP_DECIDED 0x1
+int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens,
+                            const int32_t* cap, const int32_t* need, const int32_t* rule_flags, const int32_t* truth,
+                            int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                            int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                            int64_t* tie_class_hits_out, int64_t* token_sum_out,
+                            int64_t* vote_count_sum_out, int64_t* truth_count_sum_out, int64_t* stop_hist_out,
+                            int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out, int32_t* cell_votes_out);
+
+/*
  * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
  * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
  * seed and nothing left to converge.
@@ -410,7 +463,7 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
 
 /*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the

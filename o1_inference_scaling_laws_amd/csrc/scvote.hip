@@ -185,6 +185,7 @@ struct scv_ctx {
     int64_t stat_expected_calls = 0;    // scv_expected_majority_i32 launches
     int64_t stat_token_budget_calls = 0;    // scv_token_budget_prefix_i32 launches
     int64_t weighted_calls = 0;             // scv_weighted_prefix_i32 launches (no stat key: the timed launches of scv_drain_kernel_ns count them)
+    int64_t adaptive_calls = 0;             // scv_adaptive_prefix_i32 launches (no stat key either)
     double* d_expected_tab = nullptr;   // scv::kExpectedTabWords: binomials and Gauss-Legendre points (written at scv_create)
 };
 
@@ -1078,6 +1079,7 @@ int check_err_word(scv_ctx* ctx, uint32_t w) {
     if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap / resample: a hit had n_modes >= M");
     if (w & 16u) return fail(SCV_ERR_ARG, "token_budget: a token count was negative; results are invalid");
     if (w & 32u) return fail(SCV_ERR_ARG, "weighted: a weight was outside 0..%d; results are invalid", SCV_WEIGHT_MAX);
+    if (w & 64u) return fail(SCV_ERR_ARG, "adaptive: a rule flag had a bit other than SCV_STOP_DECIDED; results are invalid");
     if (w & 8u) return fail(SCV_ERR_ARG, "prefix_path = 5 promised budgets that are 0, a power of two or >= N: the list in n_valid is not; nothing was computed");
     return SCV_OK;
 }
@@ -1929,6 +1931,108 @@ int weighted_host(scv_ctx* ctx, const int32_t* pool, const int32_t* weights, con
     SCV_HIP(hipStreamSynchronize(s));
     return check_err_word(ctx, w);
 }
+// scv_adaptive_prefix_i32 on device pointers: one launch of the adaptive body of scv_resample_prefix<true> (scvote_adaptive.hip.h),
+// accumulating into the per-rule outputs and overwriting the cells.
+int launch_adaptive(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* cap, const int32_t* need,
+                    const int32_t* rule_flags, const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                    int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum,
+                    int64_t* truth_sum, int64_t* stop_hist, int64_t* per_resample, scv_cell* cells, int64_t* cell_tokens, int32_t* cell_votes,
+                    uint32_t* err) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    if (P == 0 || R == 0) return SCV_OK;
+    const bool shuffled = order == SCV_ORDER_SHUFFLED;
+    scv::ResampleArgs a{};
+    a.pool = pool; a.tokens = tokens; a.truth = truth;
+    a.P = P; a.p_offset = p_offset; a.seed = seed;
+    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
+    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
+    a.token_sum = tokens ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
+    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
+    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
+    a.err_flag = err;
+    a.mode = scv::kResampleModeAdaptive;
+    a.order = shuffled ? scv::kOrderShuffled : scv::kOrderPool;
+    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens; a.cell_votes_out = cell_votes;
+    a.cap = cap; a.need = need; a.rule_flags = rule_flags;
+    a.stop_hist = reinterpret_cast<unsigned long long*>(stop_hist);
+    return launch_lane_body(ctx, pick_resample_kernel(true), a,
+                            [&](int lanes, int np) { return scv::adaptive_lds_words((int)N, B, lanes, np, shuffled); }, "adaptive",
+                            &ctx->adaptive_calls);
+}
+
+// HOST mode: chunks of problems (pool, tokens, truth; the rules once) staged through the context's device buffer, as token_budget_host
+// does: the per-rule sums, the stop histogram and per_resample are zeroed once and accumulate over the chunks on the device; each chunk's
+// cells come back behind its launch, one stream sync per chunk.  The sums and the error word are downloaded once, at the end.
+int adaptive_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* cap, const int32_t* need, const int32_t* rule_flags,
+                  const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end,
+                  uint64_t seed, int32_t M, int64_t* tie_out, int64_t* tok_out, int64_t* votes_out, int64_t* tcs_out, int64_t* hist_out,
+                  int64_t* per_out, scv_cell* cells_out, int64_t* cell_tokens_out, int32_t* cell_votes_out) {
+    const int64_t R = (int64_t)r_end - r_begin;
+    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
+    const size_t hist_bytes = (size_t)B * (N + 1) * sizeof(int64_t), need_bytes = (size_t)B * (N + 1) * sizeof(int32_t);
+    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
+    const size_t row_bytes = (tokens ? 2 : 1) * (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (cells_out ? (size_t)B * sizeof(scv_cell) : 0) +
+                             (cell_tokens_out ? (size_t)B * sizeof(int64_t) : 0) + (cell_votes_out ? (size_t)B * sizeof(int32_t) : 0);
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
+    size_t off = 0;
+    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
+    const size_t o_tok = off; off = align_up(off + (tokens ? (size_t)chunk * N * sizeof(int32_t) : 0), 256);
+    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
+    const size_t o_cap = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
+    const size_t o_flags = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
+    const size_t o_need = off; off = align_up(off + need_bytes, 256);
+    const size_t o_cells = off; off = align_up(off + (cells_out ? (size_t)chunk * B * sizeof(scv_cell) : 0), 256);
+    const size_t o_ct = off; off = align_up(off + (cell_tokens_out ? (size_t)chunk * B * sizeof(int64_t) : 0), 256);
+    const size_t o_cv = off; off = align_up(off + (cell_votes_out ? (size_t)chunk * B * sizeof(int32_t) : 0), 256);
+    const size_t o_out = off;                                                        // tie | token sums | vote sums | truth sums | stop histogram | per_resample | error word
+    const size_t o_ts = o_out + tie_bytes, o_vs = o_ts + sums_bytes, o_tc = o_vs + sums_bytes, o_hist = o_tc + sums_bytes, o_per = o_hist + hist_bytes;
+    const size_t o_err = align_up(o_per + per_bytes, 256);
+    const size_t total = o_err + 256;
+    if (int rc = ensure_stage(ctx, total)) return rc;
+    char* db = static_cast<char*>(ctx->d_stage);
+    hipStream_t s = ctx->stream;
+    SCV_HIP(hipMemcpyAsync(db + o_cap, cap, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (rule_flags) SCV_HIP(hipMemcpyAsync(db + o_flags, rule_flags, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    SCV_HIP(hipMemcpyAsync(db + o_need, need, need_bytes, hipMemcpyHostToDevice, s));
+    SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
+    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
+        const int64_t np = std::min<int64_t>(chunk, P - p0);
+        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (tokens) SCV_HIP(hipMemcpyAsync(db + o_tok, tokens + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (int rc = launch_adaptive(ctx, reinterpret_cast<const int32_t*>(db + o_pool),
+                                     tokens ? reinterpret_cast<const int32_t*>(db + o_tok) : nullptr, reinterpret_cast<const int32_t*>(db + o_cap),
+                                     reinterpret_cast<const int32_t*>(db + o_need),
+                                     rule_flags ? reinterpret_cast<const int32_t*>(db + o_flags) : nullptr,
+                                     reinterpret_cast<const int32_t*>(db + o_truth), np, B, N, p_offset + p0, order, r_begin, r_end, seed, M,
+                                     reinterpret_cast<int64_t*>(db + o_out), reinterpret_cast<int64_t*>(db + o_ts),
+                                     reinterpret_cast<int64_t*>(db + o_vs), reinterpret_cast<int64_t*>(db + o_tc),
+                                     reinterpret_cast<int64_t*>(db + o_hist), per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
+                                     cells_out ? reinterpret_cast<scv_cell*>(db + o_cells) : nullptr,
+                                     cell_tokens_out ? reinterpret_cast<int64_t*>(db + o_ct) : nullptr,
+                                     cell_votes_out ? reinterpret_cast<int32_t*>(db + o_cv) : nullptr, reinterpret_cast<uint32_t*>(db + o_err))) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        if (cells_out) SCV_HIP(hipMemcpyAsync(cells_out + p0 * B, db + o_cells, (size_t)np * B * sizeof(scv_cell), hipMemcpyDeviceToHost, s));
+        if (cell_tokens_out)
+            SCV_HIP(hipMemcpyAsync(cell_tokens_out + p0 * B, db + o_ct, (size_t)np * B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        if (cell_votes_out)
+            SCV_HIP(hipMemcpyAsync(cell_votes_out + p0 * B, db + o_cv, (size_t)np * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipStreamSynchronize(s));
+    }
+    uint32_t w = 0;
+    SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
+    if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
+    if (votes_out) SCV_HIP(hipMemcpyAsync(votes_out, db + o_vs, sums_bytes, hipMemcpyDeviceToHost, s));
+    if (tcs_out) SCV_HIP(hipMemcpyAsync(tcs_out, db + o_tc, sums_bytes, hipMemcpyDeviceToHost, s));
+    if (hist_out) SCV_HIP(hipMemcpyAsync(hist_out, db + o_hist, hist_bytes, hipMemcpyDeviceToHost, s));
+    if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipStreamSynchronize(s));
+    return check_err_word(ctx, w);
+}
 }  // namespace
 
 extern "C" {
@@ -2129,6 +2233,51 @@ int scv_weighted_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* we
         }
         return weighted_host(ctx, pool, weights, tokens, n_valid, truth, P, B, N, p_offset, rule, order, r_begin, r_end, seed, M,
                              tie_class_hits_out, token_sum_out, per_resample_out, cells_out, cell_tokens_out);
+    });
+}
+
+int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* cap, const int32_t* need,
+                            const int32_t* rule_flags, const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                            int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind, int64_t* tie_class_hits_out,
+                            int64_t* token_sum_out, int64_t* vote_count_sum_out, int64_t* truth_count_sum_out, int64_t* stop_hist_out,
+                            int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out, int32_t* cell_votes_out) {
+    return guarded([&]() -> int {
+        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
+        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
+            return fail(SCV_ERR_ARG, "adaptive: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
+                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
+        if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "adaptive: bad order %d", order);
+        if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
+            return fail(SCV_ERR_ARG, "adaptive: SCV_ORDER_POOL is one draw: r_begin = 0, r_end = 1 (got [%d,%d))", r_begin, r_end);
+        if (order == SCV_ORDER_SHUFFLED && (cells_out || cell_tokens_out || cell_votes_out))
+            return fail(SCV_ERR_ARG, "adaptive: cells_out / cell_tokens_out / cell_votes_out are written in SCV_ORDER_POOL only");
+        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "adaptive: P * (r_end - r_begin) exceeds 2^62");
+        if (!cap || !need || !tie_class_hits_out) return fail(SCV_ERR_ARG, "adaptive: cap, need and tie_class_hits_out are required");
+        if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "adaptive: pool and truth are required");
+        if ((token_sum_out || cell_tokens_out) && !tokens) return fail(SCV_ERR_ARG, "adaptive: token_sum_out / cell_tokens_out need tokens");
+        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "adaptive: per_resample_out needs M >= 1 (got %d)", M);
+        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        if (mem_kind == SCV_MEM_HOST && rule_flags)                                // (DEVICE mode: the kernel checks, error bit 6 at scv_sync)
+            for (int32_t b = 0; b < B; ++b)
+                if (rule_flags[b] & ~(int32_t)SCV_STOP_DECIDED) return fail(SCV_ERR_ARG, "adaptive: rule_flags[%d] = 0x%x has a bit other than SCV_STOP_DECIDED", b, (unsigned)rule_flags[b]);
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_adaptive(ctx, pool, tokens, cap, need, rule_flags, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
+                                   tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, stop_hist_out, per_resample_out,
+                                   cells_out, cell_tokens_out, cell_votes_out, ctx->d_err);
+        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing voted, all zero
+            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
+            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (vote_count_sum_out) memset(vote_count_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
+            if (stop_hist_out) memset(stop_hist_out, 0, (size_t)B * (N + 1) * sizeof(int64_t));
+            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
+            return SCV_OK;
+        }
+        return adaptive_host(ctx, pool, tokens, cap, need, rule_flags, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
+                             tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, stop_hist_out, per_resample_out,
+                             cells_out, cell_tokens_out, cell_votes_out);
     });
 }
 

@@ -90,9 +90,15 @@ struct ResampleArgs {
     const int32_t* weights;                              // [P, N] in 0 .. SCV_WEIGHT_MAX
     int32_t rule;                                        // 0: W(v) = sum of the weights (SCV_RULE_WEIGHT_SUM) | 1: their maximum (SCV_RULE_BEST_OF)
     int32_t wlds;                                        // rows staged in LDS as code | weight << 8 words (weighted_rows_in_lds)
+    // appended for the adaptive vote (scv_adaptive_prefix_i32, scvote_adaptive.hip.h): n_valid and budgets are unused, tokens may be NULL
+    const int32_t* cap; const int32_t* need;             // [B] sample caps | [B, N + 1] stopping table: stop when c1 >= need[b][c2]
+    const int32_t* rule_flags;                           // [B] (NULL: all 0) bit 0: SCV_STOP_DECIDED
+    unsigned long long* stop_hist;                       // [B, N + 1] cells that stopped after n samples (NULL ok)
+    int32_t* cell_votes_out;                             // [P, B] (NULL ok; pool order only), overwritten
 };
 using ResampleFn = void (*)(const ResampleArgs);
-constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3;
+constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3,
+                  kResampleModeAdaptive = 4;
 constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
 // LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
 // budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
@@ -100,6 +106,13 @@ constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV
 constexpr long long token_budget_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
     return 64 + 6LL * B + 32 + (long long)B * (N + 1) + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) +
            (shuffled ? 2LL : 1LL) * lanes * ((N + 3) / 4);
+}
+// LDS words of an adaptive-vote workgroup (scvote_adaptive.hip.h, in this order): per-rule sums (3 B int64) | caps [32] | rule masks [2] |
+// tie classes [B][N + 1] | stop lengths [B][N + 1] | need as uint16 [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and
+// distinct count [np_max][2] | the rows as byte codes [np_max][N4] | the lanes' counts [N4][lanes] | their Fisher-Yates arrays (shuffled only)
+constexpr long long adaptive_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
+    return 6LL * B + 32 + 2 + 2LL * B * (N + 1) + ((long long)B * (N + 1) + 1) / 2 + 64LL * (lanes / 64) + 2LL * np_max +
+           (long long)np_max * ((N + 3) / 4) + (shuffled ? 2LL : 1LL) * lanes * ((N + 3) / 4);
 }
 // The weighted body stages a row as N words (code | weight << 8) when a chunk of lanes touches few rows, R >= kWeightedLdsRowsMinR (at most
 // lanes / R + 2 rows); below that -- and in pool order, R = 1 -- as byte codes, with the weight read from global memory: lanes + 1 rows of N words

@@ -31,7 +31,8 @@
 // LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
 // The <false> instantiation has two more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h)
 // and the weighted vote / best-of-N (mode kResampleModeWeighted, scvote_weighted.hip.h); the <true> one the vote over the longest prefix
-// that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h).
+// that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h) and the vote that stops by a rule on its own state
+// (mode kResampleModeAdaptive, scvote_adaptive.hip.h).
 #pragma once
 
 #include "scvote_kernels.hip.h"
@@ -105,6 +106,7 @@ __device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64
 #include "scvote_expected.hip.h"
 #include "scvote_budget.hip.h"
 #include "scvote_weighted.hip.h"
+#include "scvote_adaptive.hip.h"
 
 namespace scv {
 
@@ -116,6 +118,7 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
         if (a.mode == kResampleModeWeighted) { weighted_body(a, smem_wg); return; }             // weighted vote / best-of-N: scvote_weighted.hip.h
     } else {
         if (a.mode == kResampleModeTokenBudget) { token_budget_body(a, smem_wg); return; }      // token budgets: scvote_budget.hip.h
+        if (a.mode == kResampleModeAdaptive) { adaptive_body(a, smem_wg); return; }             // stopping rules: scvote_adaptive.hip.h
     }
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lanes = (int)blockDim.x, nwaves = lanes >> 6;

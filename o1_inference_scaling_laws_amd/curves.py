@@ -5,7 +5,8 @@ The reference's majority-vote tail (o1.py:266-277: T >= 2^11 votes over the firs
 is one ordering of the cache.  ``expected_majority_records`` averages each point over ``resamples`` random orderings of the same
 pool and returns it in the reference's log schema, so plot_helpers can draw the smoothed tail next to the single-ordering one.
 ``exact_majority_records`` gives the limit of that average -- the mean over all k-subsets -- with no seed and no resample count.
-``token_budget_records`` ends each vote where a budget of TOKENS runs out instead of after a number of samples."""
+``token_budget_records`` ends each vote where a budget of TOKENS runs out instead of after a number of samples;
+``adaptive_vote_records`` where a stopping rule on the vote's own state says it is settled."""
 from __future__ import annotations
 
 import numpy as np
@@ -85,3 +86,19 @@ def weighted_majority_records(engine, pool, weights, truth, tokens, token_limits
     res = engine.weighted_prefix(pool, weights, truth, ns, rule=rule, resamples=resamples, seed=seed, M=0, tokens=tokens)
     return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
             for b, (t, _n) in enumerate(budgets)]
+
+
+def adaptive_vote_records(engine, pool, truth, tokens, rules, resamples: int | None = None, seed: int = 0):
+    """pool / tokens int32 [P, Npool] (each problem's samples in cache order; tokens may be None), truth int32 [P].  ``rules``: a list of
+    (cap, need, flags) -- the most samples the rule may draw, its stopping table int32 [Npool + 1] (adaptive.never / margin_rule /
+    beta_rule) and 0 or STOP_DECIDED.  For every rule: the accuracy of the vote that samples until the rule stops it
+    (Engine.adaptive_prefix, scv_adaptive_prefix_i32) -- in the cache order (``resamples=None``, one draw) or averaged over ``resamples``
+    random orderings -- and what it actually spent, as records {'rule', 'accuracy', 'avg_votes', 'avg_tokens_used'}: accuracy against
+    samples or tokens spent is the curve of a stopping policy (avg_tokens_used is 0.0 without tokens)."""
+    pool = np.asarray(pool, dtype=np.int32)
+    cap = np.array([int(c) for c, _n, _f in rules], dtype=np.int32)
+    need = np.stack([np.asarray(n, dtype=np.int32) for _c, n, _f in rules])
+    flags = np.array([int(f) for _c, _n, f in rules], dtype=np.int32)
+    res = engine.adaptive_prefix(pool, truth, cap, need, flags, tokens=tokens, resamples=resamples, seed=seed, M=0)
+    return [{"rule": b, "accuracy": res.accuracy(b), "avg_votes": float(res.avg_votes(b)),
+             "avg_tokens_used": float(res.avg_tokens_used(b)) if tokens is not None else 0.0} for b in range(len(rules))]

@@ -22,6 +22,7 @@ from .expected import ExpectedResult
 from .resample import ResampleResult
 from .token_budget import TokenBudgetResult
 from .weighted import WeightedResult
+from .adaptive import AdaptiveResult, check_rules
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
 CELL_DTYPE = np.dtype(
@@ -397,6 +398,51 @@ class Engine:
                                               _np_ptr(tok), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
         return WeightedResult(P, R, tie, tok, per, cells, cell_tokens)
 
+    def adaptive_prefix(self, pool, truth, cap, need, rule_flags=None, tokens=None, resamples: int | None = None, seed: int = 0,
+                        r_begin: int = 0, p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> AdaptiveResult:
+        """Majority vote that samples until a stopping rule says it is settled (scv_adaptive_prefix_i32; CPU mirror and rule builders:
+        adaptive.py).  pool int32 [P, N] (numpy, N <= 256), truth [P], cap int32 [B] (B <= 32: the most samples rule b may draw), need
+        int32 [B, N + 1] (stop when c1 >= need[b][c2]; one row [N + 1] is used for every rule), rule_flags int32 [B] or None
+        (STOP_DECIDED), tokens [P, N] or None.  ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells, cell
+        tokens and cell votes); otherwise the orderings r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of
+        ``per_resample`` (None: N + 1, which no hit can exceed; 0: not computed).  Blocking."""
+        pool = np.ascontiguousarray(pool, dtype=np.int32)
+        if pool.ndim != 2:
+            raise ValueError("pool must be [P, N]")
+        P, N = pool.shape
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        if truth.shape != (P,):
+            raise ValueError("truth must be [P]")
+        cap, need, flags = check_rules(cap, need, rule_flags, N)
+        B = cap.shape[0]
+        if tokens is not None:
+            tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+            if tokens.shape != pool.shape:
+                raise ValueError("tokens must match pool")
+        shuffled = resamples is not None
+        if want_cells and shuffled:
+            raise ValueError("cells are written in pool order only (resamples=None)")
+        r0, r1 = (int(r_begin), int(r_begin) + int(resamples)) if shuffled else (int(r_begin), int(r_begin) + 1)
+        R = r1 - r0
+        if M is None:
+            M = N + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64) if tokens is not None else None
+        votes = np.zeros((B,), dtype=np.int64)
+        tcs = np.zeros((B,), dtype=np.int64)
+        hist = np.zeros((B, N + 1), dtype=np.int64)
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
+        cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells and tokens is not None else None
+        cell_votes = np.zeros((P, B), dtype=np.int32) if want_cells else None
+        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+        check(self._L.scv_adaptive_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(cap), _np_ptr(need),
+                                              _np_ptr(flags) if rule_flags is not None else None, _np_ptr(truth), P, B, N, p_offset, order,
+                                              r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok), _np_ptr(votes),
+                                              _np_ptr(tcs), _np_ptr(hist), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens),
+                                              _np_ptr(cell_votes)))
+        return AdaptiveResult(P, R, tie, tok, votes, tcs, hist, per, cells, cell_tokens, cell_votes)
+
     # ---- DEVICE mode (torch tensors; asynchronous on torch's current stream) --------------------
 
     def _device_call(self, votes, votes_name, row_shape, truth, tokens, n_valid, counters, cells, cell_tokens, overwrite, want_no_cells=True):
@@ -695,6 +741,66 @@ class Engine:
                                               int(rule), order, r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE,
                                               ptr(tie_class_hits), ptr(token_sum), ptr(per_resample), ptr(cells), ptr(cell_tokens)))
         return tie_class_hits, token_sum, per_resample, cells, cell_tokens
+
+    def adaptive_prefix_device(self, pool, truth, cap, need, rule_flags=None, tokens=None, r_begin: int = 0, r_end: int | None = None,
+                               seed: int = 0, p_offset: int = 0, tie_class_hits=None, token_sum=None, vote_count_sum=None,
+                               truth_count_sum=None, stop_hist=None, per_resample=None, M: int | None = None, cells=None, cell_tokens=None,
+                               cell_votes=None, want_cells: bool = False):
+        """DEVICE-mode adaptive_prefix: pool (/ tokens) torch.int32 cuda [P, N], truth [P], cap [B], need [B, N + 1], rule_flags [B] or
+        None.  ``r_end=None``: the pool's own order (r_begin must be 0); otherwise the orderings [r_begin, r_end).  ACCUMULATES into the
+        given int64 buffers (tie_class_hits [B, 1025], token_sum -- with tokens --, vote_count_sum, truth_count_sum [B], stop_hist
+        [B, N + 1], per_resample [r_end - r_begin, B, M]; those left None are allocated zeroed -- per_resample only when ``M`` is given).
+        Pool order only: OVERWRITES cells (uint8 [P, B, 16]), cell_tokens (int64 [P, B], with tokens) and cell_votes (int32 [P, B]),
+        allocated when ``want_cells``.  One launch on torch's current stream, does not synchronise (an unknown rule flag is reported by
+        ``sync``).  Returns (tie_class_hits, token_sum, vote_count_sum, truth_count_sum, stop_hist, per_resample, cells, cell_tokens,
+        cell_votes)."""
+        import torch
+        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
+            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
+        self._check_device(pool, "pool")
+        P, N = int(pool.shape[0]), int(pool.shape[1])
+        dev = pool.device
+        B = int(cap.shape[0])
+        for name, t, shape in (("tokens", tokens, (P, N)), ("truth", truth, (P,)), ("cap", cap, (B,)), ("need", need, (B, N + 1)),
+                               ("rule_flags", rule_flags, (B,))):
+            if t is None and name in ("tokens", "rule_flags"):
+                continue
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
+        shuffled = r_end is not None
+        if not shuffled:
+            r_end = int(r_begin) + 1
+        R = int(r_end) - int(r_begin)
+
+        def buf(t, shape, name, dt=torch.int64):
+            if t is None:
+                return torch.zeros(shape, dtype=dt, device=dev)
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
+                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {tuple(shape)} on {dev}")
+            return t
+        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
+        token_sum = buf(token_sum, (B,), "token_sum") if tokens is not None else None
+        vote_count_sum = buf(vote_count_sum, (B,), "vote_count_sum")
+        truth_count_sum = buf(truth_count_sum, (B,), "truth_count_sum")
+        stop_hist = buf(stop_hist, (B, N + 1), "stop_hist")
+        if per_resample is not None and M is None:
+            M = int(per_resample.shape[2])
+        if M is not None:
+            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        if want_cells or cells is not None:
+            cells = buf(cells, (P, B, 16), "cells", torch.uint8)
+        if (want_cells and tokens is not None) or cell_tokens is not None:
+            cell_tokens = buf(cell_tokens, (P, B), "cell_tokens")
+        if want_cells or cell_votes is not None:
+            cell_votes = buf(cell_votes, (P, B), "cell_votes", torch.int32)
+        self.use_torch_stream()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+        check(self._L.scv_adaptive_prefix_i32(self._ctx, ptr(pool), ptr(tokens), ptr(cap), ptr(need), ptr(rule_flags), ptr(truth), P, B, N,
+                                              p_offset, order, r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE,
+                                              ptr(tie_class_hits), ptr(token_sum), ptr(vote_count_sum), ptr(truth_count_sum), ptr(stop_hist),
+                                              ptr(per_resample), ptr(cells), ptr(cell_tokens), ptr(cell_votes)))
+        return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, stop_hist, per_resample, cells, cell_tokens, cell_votes
 
 
 class MultiDeviceEngine:
