@@ -184,8 +184,6 @@ struct scv_ctx {
     int64_t stat_resample_calls = 0;    // scv_resample_prefix_i32 calls that launched the kernel
     int64_t stat_expected_calls = 0;    // scv_expected_majority_i32 launches
     int64_t stat_token_budget_calls = 0;    // scv_token_budget_prefix_i32 launches
-    int64_t weighted_calls = 0;             // scv_weighted_prefix_i32 launches (no stat key: the timed launches of scv_drain_kernel_ns count them)
-    int64_t adaptive_calls = 0;             // scv_adaptive_prefix_i32 launches (no stat key either)
     double* d_expected_tab = nullptr;   // scv::kExpectedTabWords: binomials and Gauss-Legendre points (written at scv_create)
 };
 
@@ -1108,6 +1106,19 @@ int ensure_stage(scv_ctx* ctx, size_t bytes) {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// The pinned block and the HBM block of the small HOST calls: "host_small_kb" KiB, or what the call needs if that is more.
+int ensure_small_block(scv_ctx* ctx, size_t total) {
+    if (total <= ctx->small_bytes) return SCV_OK;
+    const size_t want = std::max((size_t)ctx->small_call_kb << 10, total);
+    if (ctx->small_h) { SCV_HIP(hipHostFree(ctx->small_h)); ctx->small_h = nullptr; }
+    if (ctx->small_d) { SCV_HIP(hipFree(ctx->small_d)); ctx->small_d = nullptr; }
+    ctx->small_bytes = 0;
+    SCV_HIP(hipHostMalloc(&ctx->small_h, want, hipHostMallocDefault));
+    SCV_HIP(hipMalloc(&ctx->small_d, want));
+    ctx->small_bytes = want;
+    return SCV_OK;
+}
+
 const std::vector<double>& expected_table();     // scv_expected_majority_i32's binomials and Gauss-Legendre points (below)
 
 }  // namespace
@@ -1457,15 +1468,7 @@ int host_small(scv_ctx* ctx, bool prefix, const int32_t* answers, const int32_t*
     const size_t o_ctok = off; off = align_up(off + (tokens ? (size_t)P * B * sizeof(int64_t) : 0), 256);
     const size_t total = off;
     if (total > (size_t)ctx->small_call_kb << 10) return SCV_OK;
-    if (total > ctx->small_bytes) {
-        const size_t want = ((size_t)ctx->small_call_kb << 10) > total ? ((size_t)ctx->small_call_kb << 10) : total;
-        if (ctx->small_h) { SCV_HIP(hipHostFree(ctx->small_h)); ctx->small_h = nullptr; }
-        if (ctx->small_d) { SCV_HIP(hipFree(ctx->small_d)); ctx->small_d = nullptr; }
-        ctx->small_bytes = 0;
-        SCV_HIP(hipHostMalloc(&ctx->small_h, want, hipHostMallocDefault));
-        SCV_HIP(hipMalloc(&ctx->small_d, want));
-        ctx->small_bytes = want;
-    }
+    if (int rc = ensure_small_block(ctx, total)) return rc;
     *taken = true;
     ctx->stat_small_calls += 1;
     char* hb = static_cast<char*>(ctx->small_h);
@@ -1545,9 +1548,11 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
 
 
 // One launch of a lane-per-(problem, ordering) body of scv_resample_prefix (the shuffle, scvote_resample.hip.h; the token budgets,
-// scvote_budget.hip.h): a.P, a.R, a.N, a.B and the body's fields are set by the caller, a.np_max here.  Workgroups of 256 / 128 / 64 lanes:
+// scvote_budget.hip.h; the weights, scvote_weighted.hip.h; the stopping rules, scvote_adaptive.hip.h): a.P, a.R, a.N, a.B and the body's fields
+// are set by the caller, a.np_max here.  Workgroups of 256 / 128 / 64 lanes:
 // the one that keeps the most waves resident per CU (LDS: lds_words(lanes, rows a chunk touches) words -- the lanes' byte arrays, the
-// problem rows, the per-budget tables), the larger on a tie (fewer tables to flush).  Persistent grid.  `what` prefixes the error message.
+// problem rows, the per-budget tables), the larger on a tie (fewer tables to flush).  Persistent grid.  `what` prefixes the error message;
+// stat_calls (NULL: the entry has no stat key) counts the launches.
 template <class LdsWords>
 int launch_lane_body(scv_ctx* ctx, scv::ResampleFn fn, scv::ResampleArgs& a, LdsWords lds_words, const char* what, int64_t* stat_calls) {
     const int64_t P = a.P, R = a.R;
@@ -1575,106 +1580,241 @@ int launch_lane_body(scv_ctx* ctx, scv::ResampleFn fn, scv::ResampleArgs& a, Lds
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)best_lanes), best_lds, ctx->stream, a);
     SCV_HIP(hipGetLastError());
     if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
-    *stat_calls += 1;
+    if (stat_calls) *stat_calls += 1;
     ctx->err_dirty = true;
     return SCV_OK;
+}
+
+// The fields of scv::ResampleArgs that every lane body reads (mode kResampleModeShuffle; what a body does not use is NULL): the launch wrappers
+// below add their mode and their own fields.  The token sums are accumulated only with tokens.
+scv::ResampleArgs lane_args(const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth, int64_t P, int32_t B, int64_t N,
+                            int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int64_t* tie, int64_t* tok_sum,
+                            int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
+    scv::ResampleArgs a{};
+    a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
+    a.P = P; a.p_offset = p_offset; a.seed = seed;
+    a.N = (int32_t)N; a.B = B; a.R = (int32_t)((int64_t)r_end - r_begin); a.r_begin = r_begin; a.M = M;
+    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
+    a.token_sum = tokens ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
+    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
+    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
+    a.err_flag = err;
+    a.order = order == SCV_ORDER_SHUFFLED ? scv::kOrderShuffled : scv::kOrderPool;
+    return a;
 }
 
 // scv_resample_prefix_i32 on device pointers: one launch of scv_resample_prefix<tok> (scvote_resample.hip.h), accumulating into the outputs.
 int launch_resample(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
                     int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
                     int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    if (P == 0 || R == 0) return SCV_OK;
-    const bool tok = tokens != nullptr;
-    scv::ResampleArgs a{};                                  // mode kResampleModeShuffle; the other bodies' fields stay NULL
-    a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
-    a.P = P; a.p_offset = p_offset; a.seed = seed;
-    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
-    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
-    a.token_sum = tok ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
-    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
-    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
-    a.err_flag = err;
-    return launch_lane_body(ctx, pick_resample_kernel(tok), a,
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    scv::ResampleArgs a = lane_args(pool, tokens, n_valid, truth, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, seed, M, tie, tok_sum,
+                                    truth_sum, per_resample, err);
+    return launch_lane_body(ctx, pick_resample_kernel(tokens != nullptr), a,
                             [&](int lanes, int np) { return scv::resample_lds_words((int)N, B, lanes, np); }, "resample", &ctx->stat_resample_calls);
 }
 
-// HOST mode: inputs and zeroed outputs in one device block behind one upload, the kernel, one download, one stream sync.  Calls that fit
-// "host_small_kb" go through the context's pinned block (the reference's own sizes); larger ones copy the caller's memory directly.
-// The kernel reports into the block's own error word.
-int resample_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
-                  int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
-                  int64_t* tie_out, int64_t* tok_out, int64_t* tcs_out, int64_t* per_out) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    const size_t pool_bytes = (size_t)P * N * sizeof(int32_t);
-    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
-    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
+// scv_token_budget_prefix_i32 on device pointers: one launch of the token-budget body of scv_resample_prefix<true> (scvote_budget.hip.h),
+// accumulating into the per-budget outputs and overwriting the cells.
+int launch_token_budget(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* budgets, const int32_t* truth,
+                        int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed,
+                        int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum, int64_t* truth_sum, int64_t* per_resample,
+                        scv_cell* cells, int64_t* cell_tokens, uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    const bool shuffled = order == SCV_ORDER_SHUFFLED;
+    scv::ResampleArgs a = lane_args(pool, tokens, nullptr, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie, tok_sum, truth_sum,
+                                    per_resample, err);
+    a.mode = scv::kResampleModeTokenBudget;
+    a.budgets = budgets;
+    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
+    return launch_lane_body(ctx, pick_resample_kernel(true), a,
+                            [&](int lanes, int np) { return scv::token_budget_lds_words((int)N, B, lanes, np, shuffled); }, "token_budget",
+                            &ctx->stat_token_budget_calls);
+}
+
+// scv_weighted_prefix_i32 on device pointers: one launch of the weighted body of scv_resample_prefix<false> (scvote_weighted.hip.h),
+// accumulating into the per-budget outputs and overwriting the cells.
+int launch_weighted(scv_ctx* ctx, const int32_t* pool, const int32_t* weights, const int32_t* tokens, const int32_t* n_valid,
+                    const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int rule, int order, int32_t r_begin,
+                    int32_t r_end, uint64_t seed, int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* per_resample, scv_cell* cells,
+                    int64_t* cell_tokens, uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    const bool shuffled = order == SCV_ORDER_SHUFFLED;
+    const bool wlds = scv::weighted_rows_in_lds((int64_t)r_end - r_begin, shuffled);
+    scv::ResampleArgs a = lane_args(pool, tokens, n_valid, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie, tok_sum, nullptr,
+                                    per_resample, err);
+    a.mode = scv::kResampleModeWeighted;
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
+    a.weights = weights; a.rule = rule; a.wlds = wlds ? 1 : 0;
+    return launch_lane_body(ctx, pick_resample_kernel(false), a,
+                            [&](int lanes, int np) { return scv::weighted_lds_words((int)N, B, lanes, np, shuffled, wlds); }, "weighted", nullptr);
+}
+
+// scv_adaptive_prefix_i32 on device pointers: one launch of the adaptive body of scv_resample_prefix<true> (scvote_adaptive.hip.h),
+// accumulating into the per-rule outputs and overwriting the cells.
+int launch_adaptive(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* cap, const int32_t* need,
+                    const int32_t* rule_flags, const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                    int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum,
+                    int64_t* truth_sum, int64_t* stop_hist, int64_t* per_resample, scv_cell* cells, int64_t* cell_tokens, int32_t* cell_votes,
+                    uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    const bool shuffled = order == SCV_ORDER_SHUFFLED;
+    scv::ResampleArgs a = lane_args(pool, tokens, nullptr, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie, tok_sum, truth_sum,
+                                    per_resample, err);
+    a.mode = scv::kResampleModeAdaptive;
+    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens; a.cell_votes_out = cell_votes;
+    a.cap = cap; a.need = need; a.rule_flags = rule_flags;
+    a.stop_hist = reinterpret_cast<unsigned long long*>(stop_hist);
+    return launch_lane_body(ctx, pick_resample_kernel(true), a,
+                            [&](int lanes, int np) { return scv::adaptive_lds_words((int)N, B, lanes, np, shuffled); }, "adaptive", nullptr);
+}
+
+// The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32 and scv_adaptive_prefix_i32 share, in
+// the order the entries have always made them; `what` names the entry in every message.  An entry's own checks keep their places in that
+// order: `early` runs behind the shape check (weighted: the rule), `own` behind the P * R bound (the pointers the entry requires).
+// cells_given: the cell outputs of the entry as its message lists them when the caller passed one, NULL when it passed none.
+// scv_resample_prefix_i32 has neither an order nor cells: it passes SCV_ORDER_SHUFFLED and NULL.
+template <class Early, class Own>
+int check_lane_call(const char* what, const scv_ctx* ctx, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin,
+                    int32_t r_end, const char* cells_given, bool per_resample, int32_t M, int mem_kind, Early early, Own own) {
+    if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
+    if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
+        return fail(SCV_ERR_ARG, "%s: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
+                    what, (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
+    if (int rc = early()) return rc;
+    if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "%s: bad order %d", what, order);
+    if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
+        return fail(SCV_ERR_ARG, "%s: SCV_ORDER_POOL is one draw: r_begin = 0, r_end = 1 (got [%d,%d))", what, r_begin, r_end);
+    if (order == SCV_ORDER_SHUFFLED && cells_given) return fail(SCV_ERR_ARG, "%s: %s are written in SCV_ORDER_POOL only", what, cells_given);
+    if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "%s: P * (r_end - r_begin) exceeds 2^62", what);
+    if (int rc = own()) return rc;
+    if (per_resample && M < 1) return fail(SCV_ERR_ARG, "%s: per_resample_out needs M >= 1 (got %d)", what, M);
+    if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+    return SCV_OK;
+}
+constexpr auto no_check = [] { return SCV_OK; };
+
+// ---- HOST-mode staging of the lane-body entries and of scv_expected_majority_i32 ---------------------------------------------------------------
+// A call is a table of regions, one per caller buffer.  ROWS regions hold `bytes` per problem and are staged a chunk of problems at a time: inputs
+// go up in front of the chunk's launch, outputs (cells, cell tokens, cell votes, scores) come back behind it.  The inputs of the whole call (budgets,
+// rules) go up ONCE; the outputs every chunk adds to (tie table, sums, stop histogram, per_resample: SUMS) are zeroed once on the device and come
+// back once, at the end, with the error word.  A region whose caller pointer is NULL is absent: no room, no copy, a NULL device pointer.
+struct Region {
+    enum Kind { IN_ROWS, IN_ONCE, OUT_ROWS, OUT_SUMS } kind;
+    void* host;
+    size_t bytes;
+    size_t off;                                             // where the region lies in the block (stage_layout)
+    char* dev;                                              // ... and in device memory (stage_bind); NULL when absent
+    bool rows() const { return kind == IN_ROWS || kind == OUT_ROWS; }
+    template <class T> T* at() const { return reinterpret_cast<T*>(dev); }
+};
+Region rows_in(const void* host, size_t bytes_per_problem) { return {Region::IN_ROWS, const_cast<void*>(host), bytes_per_problem, 0, nullptr}; }
+Region once_in(const void* host, size_t bytes) { return {Region::IN_ONCE, const_cast<void*>(host), bytes, 0, nullptr}; }
+Region rows_out(void* host, size_t bytes_per_problem) { return {Region::OUT_ROWS, host, bytes_per_problem, 0, nullptr}; }
+Region sums_out(void* host, size_t bytes) { return {Region::OUT_SUMS, host, bytes, 0, nullptr}; }
+
+constexpr size_t kStageChunkBytes = (size_t)64 << 20;     // ROWS bytes of one chunk: bounds the device block whatever P is
+constexpr size_t kWholeCall = (size_t)1 << 62;            // ... of a call that must stay one launch (scv_resample_prefix_i32)
+
+// The block for chunks of `chunk` problems: [ every region but the sums, 256-byte aligned, in table order | the sums, back to back | error word ].
+// Sets the regions' offsets; *o_sums, *o_err: where the sums and the error word begin.  Returns the size of the block.
+size_t stage_layout(Region* rg, int n, int64_t chunk, size_t* o_sums, size_t* o_err) {
     size_t off = 0;
-    const size_t o_pool = off; off = align_up(off + pool_bytes, 256);
-    const size_t o_tok = off; off = align_up(off + (tokens ? pool_bytes : 0), 256);
-    const size_t o_truth = off; off = align_up(off + (size_t)P * sizeof(int32_t), 256);
-    const size_t o_nv = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
-    const size_t o_out = off;                                                        // tie | token sums | truth sums | per_resample | error word
-    const size_t o_ts = o_out + tie_bytes, o_tc = o_ts + sums_bytes, o_per = o_tc + sums_bytes;
-    const size_t o_err = align_up(o_per + per_bytes, 256);
-    const size_t total = o_err + 256;
-    const bool small = ctx->small_call_kb > 0 && total <= ((size_t)ctx->small_call_kb << 10);
-    hipStream_t s = ctx->stream;
-    char* db = nullptr;
-    char* hb = nullptr;
-    if (small) {
-        if (total > ctx->small_bytes) {
-            const size_t want = (size_t)ctx->small_call_kb << 10;
-            if (ctx->small_h) { SCV_HIP(hipHostFree(ctx->small_h)); ctx->small_h = nullptr; }
-            if (ctx->small_d) { SCV_HIP(hipFree(ctx->small_d)); ctx->small_d = nullptr; }
-            ctx->small_bytes = 0;
-            SCV_HIP(hipHostMalloc(&ctx->small_h, want, hipHostMallocDefault));
-            SCV_HIP(hipMalloc(&ctx->small_d, want));
-            ctx->small_bytes = want;
-        }
-        hb = static_cast<char*>(ctx->small_h);
-        db = static_cast<char*>(ctx->small_d);
-        memcpy(hb + o_pool, pool, pool_bytes);
-        if (tokens) memcpy(hb + o_tok, tokens, pool_bytes);
-        memcpy(hb + o_truth, truth, (size_t)P * sizeof(int32_t));
-        memcpy(hb + o_nv, n_valid, (size_t)B * sizeof(int32_t));
-        memset(hb + o_out, 0, total - o_out);
-        SCV_HIP(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, s));
-    } else {
-        if (int rc = ensure_stage(ctx, total)) return rc;
-        db = static_cast<char*>(ctx->d_stage);
-        SCV_HIP(hipMemcpyAsync(db + o_pool, pool, pool_bytes, hipMemcpyHostToDevice, s));
-        if (tokens) SCV_HIP(hipMemcpyAsync(db + o_tok, tokens, pool_bytes, hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_truth, truth, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_nv, n_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
+    for (Region* r = rg; r != rg + n; ++r) {
+        if (r->kind == Region::OUT_SUMS) continue;
+        r->off = off;
+        off = align_up(off + (r->host ? r->bytes * (r->rows() ? (size_t)chunk : 1) : 0), 256);
     }
-    if (int rc = launch_resample(ctx, reinterpret_cast<const int32_t*>(db + o_pool), tokens ? reinterpret_cast<const int32_t*>(db + o_tok) : nullptr,
-                                 reinterpret_cast<const int32_t*>(db + o_nv), reinterpret_cast<const int32_t*>(db + o_truth), P, B, N, p_offset,
-                                 r_begin, r_end, seed, M, reinterpret_cast<int64_t*>(db + o_out), reinterpret_cast<int64_t*>(db + o_ts),
-                                 reinterpret_cast<int64_t*>(db + o_tc), per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
-                                 reinterpret_cast<uint32_t*>(db + o_err))) {
+    *o_sums = off;
+    for (Region* r = rg; r != rg + n; ++r) {
+        if (r->kind != Region::OUT_SUMS) continue;
+        r->off = off;
+        off += r->host ? r->bytes : 0;
+    }
+    *o_err = align_up(off, 256);
+    return *o_err + 256;
+}
+
+void stage_bind(Region* rg, int n, char* base) {
+    for (Region* r = rg; r != rg + n; ++r) r->dev = r->host ? base + r->off : nullptr;
+}
+
+// A HOST call with nothing to vote on overwrites too: every output all zero.
+int zero_outputs(const Region* rg, int n, int64_t P) {
+    for (const Region* r = rg; r != rg + n; ++r)
+        if (r->host && (r->kind == Region::OUT_ROWS || r->kind == Region::OUT_SUMS)) memset(r->host, 0, r->bytes * (r->rows() ? (size_t)P : 1));
+    return SCV_OK;
+}
+
+// Runs a HOST call of P > 0 problems through the context's staging buffer, in chunks of as many problems as chunk_bytes of the present ROWS
+// regions hold (at least one, at most P).  launch(np, p0, err) queues the kernel for problems [p0, p0 + np) on the regions' dev pointers; the
+// kernels report into the block's own error word.  One stream sync between chunks (the next chunk overwrites the staged rows), one at the end.
+template <class Launch>
+int stage_call(scv_ctx* ctx, Region* rg, int n, int64_t P, size_t chunk_bytes, Launch launch) {
+    size_t row_bytes = 0;
+    for (const Region* r = rg; r != rg + n; ++r) if (r->host && r->rows()) row_bytes += r->bytes;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(chunk_bytes / row_bytes)));
+    size_t o_sums = 0, o_err = 0;
+    const size_t total = stage_layout(rg, n, chunk, &o_sums, &o_err);
+    if (int rc = ensure_stage(ctx, total)) return rc;
+    char* db = static_cast<char*>(ctx->d_stage);
+    stage_bind(rg, n, db);
+    uint32_t* d_err = reinterpret_cast<uint32_t*>(db + o_err);
+    hipStream_t s = ctx->stream;
+    for (const Region* r = rg; r != rg + n; ++r)
+        if (r->host && r->kind == Region::IN_ONCE) SCV_HIP(hipMemcpyAsync(r->dev, r->host, r->bytes, hipMemcpyHostToDevice, s));
+    SCV_HIP(hipMemsetAsync(db + o_sums, 0, total - o_sums, s));
+    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
+        const int64_t np = std::min<int64_t>(chunk, P - p0);
+        for (const Region* r = rg; r != rg + n; ++r)
+            if (r->host && r->kind == Region::IN_ROWS)
+                SCV_HIP(hipMemcpyAsync(r->dev, static_cast<const char*>(r->host) + (size_t)p0 * r->bytes, (size_t)np * r->bytes, hipMemcpyHostToDevice, s));
+        if (int rc = launch(np, p0, d_err)) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        for (const Region* r = rg; r != rg + n; ++r)
+            if (r->host && r->kind == Region::OUT_ROWS)
+                SCV_HIP(hipMemcpyAsync(static_cast<char*>(r->host) + (size_t)p0 * r->bytes, r->dev, (size_t)np * r->bytes, hipMemcpyDeviceToHost, s));
+        if (p0 + np < P) SCV_HIP(hipStreamSynchronize(s));
+    }
+    uint32_t w = 0;
+    for (const Region* r = rg; r != rg + n; ++r)
+        if (r->host && r->kind == Region::OUT_SUMS) SCV_HIP(hipMemcpyAsync(r->host, r->dev, r->bytes, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipMemcpyAsync(&w, d_err, sizeof w, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipStreamSynchronize(s));
+    return check_err_word(ctx, w);
+}
+
+// scv_resample_prefix_i32 in HOST mode: ONE launch per call whatever its size.  Calls that fit "host_small_kb" (the reference's own sizes) go
+// through the context's pinned block -- host memcpy in, one upload of the whole block, the kernel, one download of the sums and the error
+// word, one stream sync, host memcpy out; larger ones through the staging buffer as a single chunk.
+template <class Launch>
+int resample_host(scv_ctx* ctx, Region* rg, int n, int64_t P, Launch launch) {
+    size_t o_sums = 0, o_err = 0;
+    const size_t total = stage_layout(rg, n, P, &o_sums, &o_err);
+    if (ctx->small_call_kb <= 0 || total > ((size_t)ctx->small_call_kb << 10)) return stage_call(ctx, rg, n, P, kWholeCall, launch);
+    if (int rc = ensure_small_block(ctx, total)) return rc;
+    char* hb = static_cast<char*>(ctx->small_h);
+    char* db = static_cast<char*>(ctx->small_d);
+    stage_bind(rg, n, db);
+    hipStream_t s = ctx->stream;
+    for (const Region* r = rg; r != rg + n; ++r)
+        if (r->host && (r->kind == Region::IN_ROWS || r->kind == Region::IN_ONCE)) memcpy(hb + r->off, r->host, r->bytes * (r->rows() ? (size_t)P : 1));
+    memset(hb + o_sums, 0, total - o_sums);
+    SCV_HIP(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, s));
+    if (int rc = launch(P, 0, reinterpret_cast<uint32_t*>(db + o_err))) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
+    SCV_HIP(hipMemcpyAsync(hb + o_sums, db + o_sums, total - o_sums, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipStreamSynchronize(s));
+    for (const Region* r = rg; r != rg + n; ++r)
+        if (r->host && r->kind == Region::OUT_SUMS) memcpy(r->host, hb + r->off, r->bytes);
     uint32_t w = 0;
-    if (small) {
-        SCV_HIP(hipMemcpyAsync(hb + o_out, db + o_out, total - o_out, hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
-        memcpy(tie_out, hb + o_out, tie_bytes);
-        if (tok_out) memcpy(tok_out, hb + o_ts, sums_bytes);
-        if (tcs_out) memcpy(tcs_out, hb + o_tc, sums_bytes);
-        if (per_out) memcpy(per_out, hb + o_per, per_bytes);
-        memcpy(&w, hb + o_err, sizeof w);
-    } else {
-        SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
-        if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
-        if (tcs_out) SCV_HIP(hipMemcpyAsync(tcs_out, db + o_tc, sums_bytes, hipMemcpyDeviceToHost, s));
-        if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
-    }
+    memcpy(&w, hb + o_err, sizeof w);
     return check_err_word(ctx, w);
 }
 
@@ -1716,323 +1856,6 @@ int launch_expected(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, c
     return SCV_OK;
 }
 
-// HOST mode: chunks of problems staged through the context's device buffer (inputs, outputs, error word), one launch, one download, one
-// stream sync per chunk; the error bits of every chunk are collected and reported at the end.
-int expected_host(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, const int32_t* truth, int64_t P, int32_t B, int64_t N,
-                  double* score_out, double* hit_out) {
-    const size_t row_bytes = (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (size_t)B * sizeof(double) * (hit_out ? 2 : 1);
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
-    size_t off = 0;
-    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
-    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
-    const size_t o_nv = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
-    const size_t o_score = off; off = align_up(off + (size_t)chunk * B * sizeof(double), 256);
-    const size_t o_hit = off; off = align_up(off + (hit_out ? (size_t)chunk * B * sizeof(double) : 0), 256);
-    const size_t o_err = off; off += 256;
-    if (int rc = ensure_stage(ctx, off)) return rc;
-    char* db = static_cast<char*>(ctx->d_stage);
-    hipStream_t s = ctx->stream;
-    SCV_HIP(hipMemcpyAsync(db + o_nv, n_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    uint32_t w_all = 0;
-    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
-        const int64_t np = std::min<int64_t>(chunk, P - p0);
-        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemsetAsync(db + o_err, 0, sizeof(uint32_t), s));
-        if (int rc = launch_expected(ctx, reinterpret_cast<const int32_t*>(db + o_pool), reinterpret_cast<const int32_t*>(db + o_nv),
-                                     reinterpret_cast<const int32_t*>(db + o_truth), np, B, N, reinterpret_cast<double*>(db + o_score),
-                                     hit_out ? reinterpret_cast<double*>(db + o_hit) : nullptr, reinterpret_cast<uint32_t*>(db + o_err))) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        uint32_t w = 0;
-        SCV_HIP(hipMemcpyAsync(score_out + p0 * B, db + o_score, (size_t)np * B * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (hit_out) SCV_HIP(hipMemcpyAsync(hit_out + p0 * B, db + o_hit, (size_t)np * B * sizeof(double), hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
-        w_all |= w;
-    }
-    return check_err_word(ctx, w_all);
-}
-
-// scv_token_budget_prefix_i32 on device pointers: one launch of the token-budget body of scv_resample_prefix<true> (scvote_budget.hip.h),
-// accumulating into the per-budget outputs and overwriting the cells.
-int launch_token_budget(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* budgets, const int32_t* truth,
-                        int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed,
-                        int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum, int64_t* truth_sum, int64_t* per_resample,
-                        scv_cell* cells, int64_t* cell_tokens, uint32_t* err) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    if (P == 0 || R == 0) return SCV_OK;
-    const bool shuffled = order == SCV_ORDER_SHUFFLED;
-    scv::ResampleArgs a{};
-    a.pool = pool; a.tokens = tokens; a.truth = truth;
-    a.P = P; a.p_offset = p_offset; a.seed = seed;
-    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
-    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
-    a.token_sum = reinterpret_cast<unsigned long long*>(tok_sum);
-    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
-    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
-    a.err_flag = err;
-    a.mode = scv::kResampleModeTokenBudget;
-    a.budgets = budgets;
-    a.order = shuffled ? scv::kOrderShuffled : scv::kOrderPool;
-    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
-    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
-    return launch_lane_body(ctx, pick_resample_kernel(true), a,
-                            [&](int lanes, int np) { return scv::token_budget_lds_words((int)N, B, lanes, np, shuffled); }, "token_budget",
-                            &ctx->stat_token_budget_calls);
-}
-
-// HOST mode: chunks of problems (pool, tokens, truth; the budgets once) staged through the context's device buffer.  The per-budget sums and
-// per_resample are zeroed once and accumulate over the chunks on the device; each chunk's cells come back behind its launch, one stream sync
-// per chunk (the next chunk overwrites the staged inputs).  The sums and the error word are downloaded once, at the end.
-int token_budget_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* budgets, const int32_t* truth, int64_t P,
-                      int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
-                      int64_t* tie_out, int64_t* tok_out, int64_t* votes_out, int64_t* tcs_out, int64_t* per_out, scv_cell* cells_out,
-                      int64_t* cell_tokens_out) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
-    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
-    const size_t row_bytes = 2 * (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (cells_out ? (size_t)B * sizeof(scv_cell) : 0) +
-                             (cell_tokens_out ? (size_t)B * sizeof(int64_t) : 0);
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
-    size_t off = 0;
-    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
-    const size_t o_tok = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
-    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
-    const size_t o_bud = off; off = align_up(off + (size_t)B * sizeof(int64_t), 256);
-    const size_t o_cells = off; off = align_up(off + (cells_out ? (size_t)chunk * B * sizeof(scv_cell) : 0), 256);
-    const size_t o_ct = off; off = align_up(off + (cell_tokens_out ? (size_t)chunk * B * sizeof(int64_t) : 0), 256);
-    const size_t o_out = off;                                                        // tie | token sums | vote sums | truth sums | per_resample | error word
-    const size_t o_ts = o_out + tie_bytes, o_vs = o_ts + sums_bytes, o_tc = o_vs + sums_bytes, o_per = o_tc + sums_bytes;
-    const size_t o_err = align_up(o_per + per_bytes, 256);
-    const size_t total = o_err + 256;
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* db = static_cast<char*>(ctx->d_stage);
-    hipStream_t s = ctx->stream;
-    SCV_HIP(hipMemcpyAsync(db + o_bud, budgets, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
-    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
-        const int64_t np = std::min<int64_t>(chunk, P - p0);
-        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_tok, tokens + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (int rc = launch_token_budget(ctx, reinterpret_cast<const int32_t*>(db + o_pool), reinterpret_cast<const int32_t*>(db + o_tok),
-                                         reinterpret_cast<const int64_t*>(db + o_bud), reinterpret_cast<const int32_t*>(db + o_truth), np, B, N,
-                                         p_offset + p0, order, r_begin, r_end, seed, M, reinterpret_cast<int64_t*>(db + o_out),
-                                         reinterpret_cast<int64_t*>(db + o_ts), reinterpret_cast<int64_t*>(db + o_vs),
-                                         reinterpret_cast<int64_t*>(db + o_tc), per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
-                                         cells_out ? reinterpret_cast<scv_cell*>(db + o_cells) : nullptr,
-                                         cell_tokens_out ? reinterpret_cast<int64_t*>(db + o_ct) : nullptr,
-                                         reinterpret_cast<uint32_t*>(db + o_err))) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        if (cells_out) SCV_HIP(hipMemcpyAsync(cells_out + p0 * B, db + o_cells, (size_t)np * B * sizeof(scv_cell), hipMemcpyDeviceToHost, s));
-        if (cell_tokens_out)
-            SCV_HIP(hipMemcpyAsync(cell_tokens_out + p0 * B, db + o_ct, (size_t)np * B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
-    }
-    uint32_t w = 0;
-    SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
-    if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (votes_out) SCV_HIP(hipMemcpyAsync(votes_out, db + o_vs, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (tcs_out) SCV_HIP(hipMemcpyAsync(tcs_out, db + o_tc, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
-    SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
-    SCV_HIP(hipStreamSynchronize(s));
-    return check_err_word(ctx, w);
-}
-
-// scv_weighted_prefix_i32 on device pointers: one launch of the weighted body of scv_resample_prefix<false> (scvote_weighted.hip.h),
-// accumulating into the per-budget outputs and overwriting the cells.
-int launch_weighted(scv_ctx* ctx, const int32_t* pool, const int32_t* weights, const int32_t* tokens, const int32_t* n_valid,
-                    const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int rule, int order, int32_t r_begin,
-                    int32_t r_end, uint64_t seed, int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* per_resample, scv_cell* cells,
-                    int64_t* cell_tokens, uint32_t* err) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    if (P == 0 || R == 0) return SCV_OK;
-    const bool shuffled = order == SCV_ORDER_SHUFFLED;
-    const bool wlds = scv::weighted_rows_in_lds(R, shuffled);
-    scv::ResampleArgs a{};
-    a.pool = pool; a.tokens = tokens; a.n_valid = n_valid; a.truth = truth;
-    a.P = P; a.p_offset = p_offset; a.seed = seed;
-    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
-    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
-    a.token_sum = tokens ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
-    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
-    a.err_flag = err;
-    a.mode = scv::kResampleModeWeighted;
-    a.order = shuffled ? scv::kOrderShuffled : scv::kOrderPool;
-    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
-    a.weights = weights; a.rule = rule; a.wlds = wlds ? 1 : 0;
-    return launch_lane_body(ctx, pick_resample_kernel(false), a,
-                            [&](int lanes, int np) { return scv::weighted_lds_words((int)N, B, lanes, np, shuffled, wlds); }, "weighted",
-                            &ctx->weighted_calls);
-}
-
-// HOST mode: chunks of problems (pool, weights, tokens, truth; the budgets once) staged through the context's device buffer, as
-// token_budget_host does: the per-budget sums and per_resample are zeroed once and accumulate over the chunks on the device; each chunk's
-// cells come back behind its launch, one stream sync per chunk.  The sums and the error word are downloaded once, at the end.
-int weighted_host(scv_ctx* ctx, const int32_t* pool, const int32_t* weights, const int32_t* tokens, const int32_t* n_valid,
-                  const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int rule, int order, int32_t r_begin, int32_t r_end,
-                  uint64_t seed, int32_t M, int64_t* tie_out, int64_t* tok_out, int64_t* per_out, scv_cell* cells_out,
-                  int64_t* cell_tokens_out) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
-    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
-    const size_t row_bytes = (tokens ? 3 : 2) * (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (cells_out ? (size_t)B * sizeof(scv_cell) : 0) +
-                             (cell_tokens_out ? (size_t)B * sizeof(int64_t) : 0);
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
-    size_t off = 0;
-    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
-    const size_t o_w = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
-    const size_t o_tok = off; off = align_up(off + (tokens ? (size_t)chunk * N * sizeof(int32_t) : 0), 256);
-    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
-    const size_t o_nv = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
-    const size_t o_cells = off; off = align_up(off + (cells_out ? (size_t)chunk * B * sizeof(scv_cell) : 0), 256);
-    const size_t o_ct = off; off = align_up(off + (cell_tokens_out ? (size_t)chunk * B * sizeof(int64_t) : 0), 256);
-    const size_t o_out = off;                                                        // tie | token sums | per_resample | error word
-    const size_t o_ts = o_out + tie_bytes, o_per = o_ts + sums_bytes;
-    const size_t o_err = align_up(o_per + per_bytes, 256);
-    const size_t total = o_err + 256;
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* db = static_cast<char*>(ctx->d_stage);
-    hipStream_t s = ctx->stream;
-    SCV_HIP(hipMemcpyAsync(db + o_nv, n_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
-    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
-        const int64_t np = std::min<int64_t>(chunk, P - p0);
-        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_w, weights + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (tokens) SCV_HIP(hipMemcpyAsync(db + o_tok, tokens + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (int rc = launch_weighted(ctx, reinterpret_cast<const int32_t*>(db + o_pool), reinterpret_cast<const int32_t*>(db + o_w),
-                                     tokens ? reinterpret_cast<const int32_t*>(db + o_tok) : nullptr, reinterpret_cast<const int32_t*>(db + o_nv),
-                                     reinterpret_cast<const int32_t*>(db + o_truth), np, B, N, p_offset + p0, rule, order, r_begin, r_end, seed, M,
-                                     reinterpret_cast<int64_t*>(db + o_out), reinterpret_cast<int64_t*>(db + o_ts),
-                                     per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
-                                     cells_out ? reinterpret_cast<scv_cell*>(db + o_cells) : nullptr,
-                                     cell_tokens_out ? reinterpret_cast<int64_t*>(db + o_ct) : nullptr,
-                                     reinterpret_cast<uint32_t*>(db + o_err))) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        if (cells_out) SCV_HIP(hipMemcpyAsync(cells_out + p0 * B, db + o_cells, (size_t)np * B * sizeof(scv_cell), hipMemcpyDeviceToHost, s));
-        if (cell_tokens_out)
-            SCV_HIP(hipMemcpyAsync(cell_tokens_out + p0 * B, db + o_ct, (size_t)np * B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
-    }
-    uint32_t w = 0;
-    SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
-    if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
-    SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
-    SCV_HIP(hipStreamSynchronize(s));
-    return check_err_word(ctx, w);
-}
-// scv_adaptive_prefix_i32 on device pointers: one launch of the adaptive body of scv_resample_prefix<true> (scvote_adaptive.hip.h),
-// accumulating into the per-rule outputs and overwriting the cells.
-int launch_adaptive(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* cap, const int32_t* need,
-                    const int32_t* rule_flags, const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
-                    int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum,
-                    int64_t* truth_sum, int64_t* stop_hist, int64_t* per_resample, scv_cell* cells, int64_t* cell_tokens, int32_t* cell_votes,
-                    uint32_t* err) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    if (P == 0 || R == 0) return SCV_OK;
-    const bool shuffled = order == SCV_ORDER_SHUFFLED;
-    scv::ResampleArgs a{};
-    a.pool = pool; a.tokens = tokens; a.truth = truth;
-    a.P = P; a.p_offset = p_offset; a.seed = seed;
-    a.N = (int32_t)N; a.B = B; a.R = (int32_t)R; a.r_begin = r_begin; a.M = M;
-    a.tie_hits = reinterpret_cast<unsigned long long*>(tie);
-    a.token_sum = tokens ? reinterpret_cast<unsigned long long*>(tok_sum) : nullptr;
-    a.truth_sum = reinterpret_cast<unsigned long long*>(truth_sum);
-    a.per_resample = reinterpret_cast<unsigned long long*>(per_resample);
-    a.err_flag = err;
-    a.mode = scv::kResampleModeAdaptive;
-    a.order = shuffled ? scv::kOrderShuffled : scv::kOrderPool;
-    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
-    a.cells_out = cells; a.cell_tokens_out = cell_tokens; a.cell_votes_out = cell_votes;
-    a.cap = cap; a.need = need; a.rule_flags = rule_flags;
-    a.stop_hist = reinterpret_cast<unsigned long long*>(stop_hist);
-    return launch_lane_body(ctx, pick_resample_kernel(true), a,
-                            [&](int lanes, int np) { return scv::adaptive_lds_words((int)N, B, lanes, np, shuffled); }, "adaptive",
-                            &ctx->adaptive_calls);
-}
-
-// HOST mode: chunks of problems (pool, tokens, truth; the rules once) staged through the context's device buffer, as token_budget_host
-// does: the per-rule sums, the stop histogram and per_resample are zeroed once and accumulate over the chunks on the device; each chunk's
-// cells come back behind its launch, one stream sync per chunk.  The sums and the error word are downloaded once, at the end.
-int adaptive_host(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* cap, const int32_t* need, const int32_t* rule_flags,
-                  const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end,
-                  uint64_t seed, int32_t M, int64_t* tie_out, int64_t* tok_out, int64_t* votes_out, int64_t* tcs_out, int64_t* hist_out,
-                  int64_t* per_out, scv_cell* cells_out, int64_t* cell_tokens_out, int32_t* cell_votes_out) {
-    const int64_t R = (int64_t)r_end - r_begin;
-    const size_t tie_bytes = (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t), sums_bytes = (size_t)B * sizeof(int64_t);
-    const size_t hist_bytes = (size_t)B * (N + 1) * sizeof(int64_t), need_bytes = (size_t)B * (N + 1) * sizeof(int32_t);
-    const size_t per_bytes = per_out ? (size_t)R * B * M * sizeof(int64_t) : 0;
-    const size_t row_bytes = (tokens ? 2 : 1) * (size_t)N * sizeof(int32_t) + sizeof(int32_t) + (cells_out ? (size_t)B * sizeof(scv_cell) : 0) +
-                             (cell_tokens_out ? (size_t)B * sizeof(int64_t) : 0) + (cell_votes_out ? (size_t)B * sizeof(int32_t) : 0);
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)((64u << 20) / row_bytes)));
-    size_t off = 0;
-    const size_t o_pool = off; off = align_up(off + (size_t)chunk * N * sizeof(int32_t), 256);
-    const size_t o_tok = off; off = align_up(off + (tokens ? (size_t)chunk * N * sizeof(int32_t) : 0), 256);
-    const size_t o_truth = off; off = align_up(off + (size_t)chunk * sizeof(int32_t), 256);
-    const size_t o_cap = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
-    const size_t o_flags = off; off = align_up(off + (size_t)B * sizeof(int32_t), 256);
-    const size_t o_need = off; off = align_up(off + need_bytes, 256);
-    const size_t o_cells = off; off = align_up(off + (cells_out ? (size_t)chunk * B * sizeof(scv_cell) : 0), 256);
-    const size_t o_ct = off; off = align_up(off + (cell_tokens_out ? (size_t)chunk * B * sizeof(int64_t) : 0), 256);
-    const size_t o_cv = off; off = align_up(off + (cell_votes_out ? (size_t)chunk * B * sizeof(int32_t) : 0), 256);
-    const size_t o_out = off;                                                        // tie | token sums | vote sums | truth sums | stop histogram | per_resample | error word
-    const size_t o_ts = o_out + tie_bytes, o_vs = o_ts + sums_bytes, o_tc = o_vs + sums_bytes, o_hist = o_tc + sums_bytes, o_per = o_hist + hist_bytes;
-    const size_t o_err = align_up(o_per + per_bytes, 256);
-    const size_t total = o_err + 256;
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* db = static_cast<char*>(ctx->d_stage);
-    hipStream_t s = ctx->stream;
-    SCV_HIP(hipMemcpyAsync(db + o_cap, cap, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (rule_flags) SCV_HIP(hipMemcpyAsync(db + o_flags, rule_flags, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    SCV_HIP(hipMemcpyAsync(db + o_need, need, need_bytes, hipMemcpyHostToDevice, s));
-    SCV_HIP(hipMemsetAsync(db + o_out, 0, total - o_out, s));
-    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
-        const int64_t np = std::min<int64_t>(chunk, P - p0);
-        SCV_HIP(hipMemcpyAsync(db + o_pool, pool + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (tokens) SCV_HIP(hipMemcpyAsync(db + o_tok, tokens + p0 * N, (size_t)np * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SCV_HIP(hipMemcpyAsync(db + o_truth, truth + p0, (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (int rc = launch_adaptive(ctx, reinterpret_cast<const int32_t*>(db + o_pool),
-                                     tokens ? reinterpret_cast<const int32_t*>(db + o_tok) : nullptr, reinterpret_cast<const int32_t*>(db + o_cap),
-                                     reinterpret_cast<const int32_t*>(db + o_need),
-                                     rule_flags ? reinterpret_cast<const int32_t*>(db + o_flags) : nullptr,
-                                     reinterpret_cast<const int32_t*>(db + o_truth), np, B, N, p_offset + p0, order, r_begin, r_end, seed, M,
-                                     reinterpret_cast<int64_t*>(db + o_out), reinterpret_cast<int64_t*>(db + o_ts),
-                                     reinterpret_cast<int64_t*>(db + o_vs), reinterpret_cast<int64_t*>(db + o_tc),
-                                     reinterpret_cast<int64_t*>(db + o_hist), per_out ? reinterpret_cast<int64_t*>(db + o_per) : nullptr,
-                                     cells_out ? reinterpret_cast<scv_cell*>(db + o_cells) : nullptr,
-                                     cell_tokens_out ? reinterpret_cast<int64_t*>(db + o_ct) : nullptr,
-                                     cell_votes_out ? reinterpret_cast<int32_t*>(db + o_cv) : nullptr, reinterpret_cast<uint32_t*>(db + o_err))) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        if (cells_out) SCV_HIP(hipMemcpyAsync(cells_out + p0 * B, db + o_cells, (size_t)np * B * sizeof(scv_cell), hipMemcpyDeviceToHost, s));
-        if (cell_tokens_out)
-            SCV_HIP(hipMemcpyAsync(cell_tokens_out + p0 * B, db + o_ct, (size_t)np * B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        if (cell_votes_out)
-            SCV_HIP(hipMemcpyAsync(cell_votes_out + p0 * B, db + o_cv, (size_t)np * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
-    }
-    uint32_t w = 0;
-    SCV_HIP(hipMemcpyAsync(tie_out, db + o_out, tie_bytes, hipMemcpyDeviceToHost, s));
-    if (tok_out) SCV_HIP(hipMemcpyAsync(tok_out, db + o_ts, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (votes_out) SCV_HIP(hipMemcpyAsync(votes_out, db + o_vs, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (tcs_out) SCV_HIP(hipMemcpyAsync(tcs_out, db + o_tc, sums_bytes, hipMemcpyDeviceToHost, s));
-    if (hist_out) SCV_HIP(hipMemcpyAsync(hist_out, db + o_hist, hist_bytes, hipMemcpyDeviceToHost, s));
-    if (per_out) SCV_HIP(hipMemcpyAsync(per_out, db + o_per, per_bytes, hipMemcpyDeviceToHost, s));
-    SCV_HIP(hipMemcpyAsync(&w, db + o_err, sizeof w, hipMemcpyDeviceToHost, s));
-    SCV_HIP(hipStreamSynchronize(s));
-    return check_err_word(ctx, w);
-}
 }  // namespace
 
 extern "C" {
@@ -2133,30 +1956,28 @@ int scv_resample_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
                             int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* truth_count_sum_out,
                             int64_t* per_resample_out) {
     return guarded([&]() -> int {
-        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
-        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
-            return fail(SCV_ERR_ARG, "resample: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
-                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
-        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "resample: P * (r_end - r_begin) exceeds 2^62");
-        if (!n_valid || !tie_class_hits_out) return fail(SCV_ERR_ARG, "resample: n_valid and tie_class_hits_out are required");
-        if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "resample: pool and truth are required");
-        if (token_sum_out && !tokens) return fail(SCV_ERR_ARG, "resample: token_sum_out needs tokens");
-        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "resample: per_resample_out needs M >= 1 (got %d)", M);
-        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        if (int rc = check_lane_call("resample", ctx, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, nullptr, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!n_valid || !tie_class_hits_out) return fail(SCV_ERR_ARG, "resample: n_valid and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "resample: pool and truth are required");
+                if (token_sum_out && !tokens) return fail(SCV_ERR_ARG, "resample: token_sum_out needs tokens");
+                return SCV_OK;
+            })) return rc;
         SCV_ENTER(ctx);
         if (!per_resample_out) M = 1;
         if (mem_kind == SCV_MEM_DEVICE)
             return launch_resample(ctx, pool, tokens, n_valid, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out,
                                    token_sum_out, truth_count_sum_out, per_resample_out, ctx->d_err);
-        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing drawn, all zero
-            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
-            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
-            return SCV_OK;
-        }
-        return resample_host(ctx, pool, tokens, n_valid, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out,
-                             token_sum_out, truth_count_sum_out, per_resample_out);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t);
+        enum { POOL, TOK, TRUTH, NV, TIE, TSUM, TCS, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(n_valid, (size_t)B * sizeof(int32_t)),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums), sums_out(truth_count_sum_out, sums),
+                       sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing drawn, all zero
+        return resample_host(ctx, rg, PER + 1, P, [&](int64_t np, int64_t p0, uint32_t* err) {
+            return launch_resample(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[NV].at<const int32_t>(),
+                                   rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
+                                   rg[TSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(), err);
+        });
     });
 }
 
@@ -2165,36 +1986,31 @@ int scv_token_budget_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t
                                 int32_t M, int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* vote_count_sum_out,
                                 int64_t* truth_count_sum_out, int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out) {
     return guarded([&]() -> int {
-        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
-        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
-            return fail(SCV_ERR_ARG, "token_budget: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
-                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
-        if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "token_budget: bad order %d", order);
-        if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
-            return fail(SCV_ERR_ARG, "token_budget: SCV_ORDER_POOL is one draw: r_begin = 0, r_end = 1 (got [%d,%d))", r_begin, r_end);
-        if (order == SCV_ORDER_SHUFFLED && (cells_out || cell_tokens_out))
-            return fail(SCV_ERR_ARG, "token_budget: cells_out / cell_tokens_out are written in SCV_ORDER_POOL only");
-        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "token_budget: P * (r_end - r_begin) exceeds 2^62");
-        if (!token_budget || !tie_class_hits_out) return fail(SCV_ERR_ARG, "token_budget: token_budget and tie_class_hits_out are required");
-        if (P > 0 && (!pool || !tokens || !truth)) return fail(SCV_ERR_ARG, "token_budget: pool, tokens and truth are required");
-        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "token_budget: per_resample_out needs M >= 1 (got %d)", M);
-        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        const char* cells_given = (cells_out || cell_tokens_out) ? "cells_out / cell_tokens_out" : nullptr;
+        if (int rc = check_lane_call("token_budget", ctx, P, B, N, p_offset, order, r_begin, r_end, cells_given, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!token_budget || !tie_class_hits_out) return fail(SCV_ERR_ARG, "token_budget: token_budget and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !tokens || !truth)) return fail(SCV_ERR_ARG, "token_budget: pool, tokens and truth are required");
+                return SCV_OK;
+            })) return rc;
         SCV_ENTER(ctx);
         if (!per_resample_out) M = 1;
         if (mem_kind == SCV_MEM_DEVICE)
             return launch_token_budget(ctx, pool, tokens, token_budget, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
                                        tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, per_resample_out, cells_out,
                                        cell_tokens_out, ctx->d_err);
-        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing voted, all zero
-            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
-            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (vote_count_sum_out) memset(vote_count_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
-            return SCV_OK;
-        }
-        return token_budget_host(ctx, pool, tokens, token_budget, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie_class_hits_out,
-                                 token_sum_out, vote_count_sum_out, truth_count_sum_out, per_resample_out, cells_out, cell_tokens_out);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t);
+        enum { POOL, TOK, TRUTH, BUD, CELLS, CTOK, TIE, TSUM, VSUM, TCS, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(token_budget, (size_t)B * sizeof(int64_t)),
+                       rows_out(cells_out, (size_t)B * sizeof(scv_cell)), rows_out(cell_tokens_out, sums),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums), sums_out(vote_count_sum_out, sums),
+                       sums_out(truth_count_sum_out, sums), sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing voted, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {
+            return launch_token_budget(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[BUD].at<const int64_t>(),
+                                       rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, order, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
+                                       rg[TSUM].at<int64_t>(), rg[VSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(),
+                                       rg[CELLS].at<scv_cell>(), rg[CTOK].at<int64_t>(), err);
+        });
     });
 }
 
@@ -2203,36 +2019,34 @@ int scv_weighted_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* we
                             int32_t r_end, uint64_t seed, int32_t M, int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out,
                             int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out) {
     return guarded([&]() -> int {
-        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
-        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
-            return fail(SCV_ERR_ARG, "weighted: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
-                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
-        if (rule != SCV_RULE_WEIGHT_SUM && rule != SCV_RULE_BEST_OF) return fail(SCV_ERR_ARG, "weighted: bad rule %d", rule);
-        if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "weighted: bad order %d", order);
-        if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
-            return fail(SCV_ERR_ARG, "weighted: SCV_ORDER_POOL is one draw: r_begin = 0, r_end = 1 (got [%d,%d))", r_begin, r_end);
-        if (order == SCV_ORDER_SHUFFLED && (cells_out || cell_tokens_out))
-            return fail(SCV_ERR_ARG, "weighted: cells_out / cell_tokens_out are written in SCV_ORDER_POOL only");
-        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "weighted: P * (r_end - r_begin) exceeds 2^62");
-        if (!n_valid || !tie_class_hits_out) return fail(SCV_ERR_ARG, "weighted: n_valid and tie_class_hits_out are required");
-        if (!weights) return fail(SCV_ERR_ARG, "weighted: weights are required");
-        if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "weighted: pool and truth are required");
-        if ((token_sum_out || cell_tokens_out) && !tokens) return fail(SCV_ERR_ARG, "weighted: token_sum_out / cell_tokens_out need tokens");
-        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "weighted: per_resample_out needs M >= 1 (got %d)", M);
-        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        const char* cells_given = (cells_out || cell_tokens_out) ? "cells_out / cell_tokens_out" : nullptr;
+        if (int rc = check_lane_call("weighted", ctx, P, B, N, p_offset, order, r_begin, r_end, cells_given, per_resample_out, M, mem_kind,
+            [&] { return rule != SCV_RULE_WEIGHT_SUM && rule != SCV_RULE_BEST_OF ? fail(SCV_ERR_ARG, "weighted: bad rule %d", rule) : SCV_OK; },
+            [&] {
+                if (!n_valid || !tie_class_hits_out) return fail(SCV_ERR_ARG, "weighted: n_valid and tie_class_hits_out are required");
+                if (!weights) return fail(SCV_ERR_ARG, "weighted: weights are required");
+                if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "weighted: pool and truth are required");
+                if ((token_sum_out || cell_tokens_out) && !tokens) return fail(SCV_ERR_ARG, "weighted: token_sum_out / cell_tokens_out need tokens");
+                return SCV_OK;
+            })) return rc;
         SCV_ENTER(ctx);
         if (!per_resample_out) M = 1;
         if (mem_kind == SCV_MEM_DEVICE)
             return launch_weighted(ctx, pool, weights, tokens, n_valid, truth, P, B, N, p_offset, rule, order, r_begin, r_end, seed, M,
                                    tie_class_hits_out, token_sum_out, per_resample_out, cells_out, cell_tokens_out, ctx->d_err);
-        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing voted, all zero
-            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
-            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
-            return SCV_OK;
-        }
-        return weighted_host(ctx, pool, weights, tokens, n_valid, truth, P, B, N, p_offset, rule, order, r_begin, r_end, seed, M,
-                             tie_class_hits_out, token_sum_out, per_resample_out, cells_out, cell_tokens_out);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t);
+        enum { POOL, WEIGHTS, TOK, TRUTH, NV, CELLS, CTOK, TIE, TSUM, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(weights, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)),
+                       once_in(n_valid, (size_t)B * sizeof(int32_t)), rows_out(cells_out, (size_t)B * sizeof(scv_cell)), rows_out(cell_tokens_out, sums),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums),
+                       sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing voted, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {
+            return launch_weighted(ctx, rg[POOL].at<const int32_t>(), rg[WEIGHTS].at<const int32_t>(), rg[TOK].at<const int32_t>(),
+                                   rg[NV].at<const int32_t>(), rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, rule, order, r_begin, r_end,
+                                   seed, M, rg[TIE].at<int64_t>(), rg[TSUM].at<int64_t>(), rg[PER].at<int64_t>(), rg[CELLS].at<scv_cell>(),
+                                   rg[CTOK].at<int64_t>(), err);
+        });
     });
 }
 
@@ -2242,21 +2056,13 @@ int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
                             int64_t* token_sum_out, int64_t* vote_count_sum_out, int64_t* truth_count_sum_out, int64_t* stop_hist_out,
                             int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out, int32_t* cell_votes_out) {
     return guarded([&]() -> int {
-        if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
-        if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
-            return fail(SCV_ERR_ARG, "adaptive: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
-                        (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
-        if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "adaptive: bad order %d", order);
-        if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
-            return fail(SCV_ERR_ARG, "adaptive: SCV_ORDER_POOL is one draw: r_begin = 0, r_end = 1 (got [%d,%d))", r_begin, r_end);
-        if (order == SCV_ORDER_SHUFFLED && (cells_out || cell_tokens_out || cell_votes_out))
-            return fail(SCV_ERR_ARG, "adaptive: cells_out / cell_tokens_out / cell_votes_out are written in SCV_ORDER_POOL only");
-        if (P > 0 && (int64_t)r_end - r_begin > (1ll << 62) / P) return fail(SCV_ERR_ARG, "adaptive: P * (r_end - r_begin) exceeds 2^62");
-        if (!cap || !need || !tie_class_hits_out) return fail(SCV_ERR_ARG, "adaptive: cap, need and tie_class_hits_out are required");
-        if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "adaptive: pool and truth are required");
-        if ((token_sum_out || cell_tokens_out) && !tokens) return fail(SCV_ERR_ARG, "adaptive: token_sum_out / cell_tokens_out need tokens");
-        if (per_resample_out && M < 1) return fail(SCV_ERR_ARG, "adaptive: per_resample_out needs M >= 1 (got %d)", M);
-        if (mem_kind != SCV_MEM_HOST && mem_kind != SCV_MEM_DEVICE) return fail(SCV_ERR_ARG, "bad mem_kind %d", mem_kind);
+        const char* cells_given = (cells_out || cell_tokens_out || cell_votes_out) ? "cells_out / cell_tokens_out / cell_votes_out" : nullptr;
+        if (int rc = check_lane_call("adaptive", ctx, P, B, N, p_offset, order, r_begin, r_end, cells_given, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!cap || !need || !tie_class_hits_out) return fail(SCV_ERR_ARG, "adaptive: cap, need and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "adaptive: pool and truth are required");
+                if ((token_sum_out || cell_tokens_out) && !tokens) return fail(SCV_ERR_ARG, "adaptive: token_sum_out / cell_tokens_out need tokens");
+                return SCV_OK;
+            })) return rc;
         if (mem_kind == SCV_MEM_HOST && rule_flags)                                // (DEVICE mode: the kernel checks, error bit 6 at scv_sync)
             for (int32_t b = 0; b < B; ++b)
                 if (rule_flags[b] & ~(int32_t)SCV_STOP_DECIDED) return fail(SCV_ERR_ARG, "adaptive: rule_flags[%d] = 0x%x has a bit other than SCV_STOP_DECIDED", b, (unsigned)rule_flags[b]);
@@ -2266,18 +2072,21 @@ int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
             return launch_adaptive(ctx, pool, tokens, cap, need, rule_flags, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
                                    tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, stop_hist_out, per_resample_out,
                                    cells_out, cell_tokens_out, cell_votes_out, ctx->d_err);
-        if (P == 0 || r_end == r_begin) {                                          // HOST mode overwrites: nothing voted, all zero
-            memset(tie_class_hits_out, 0, (size_t)B * SCV_TIE_CLASSES * sizeof(int64_t));
-            if (token_sum_out) memset(token_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (vote_count_sum_out) memset(vote_count_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (truth_count_sum_out) memset(truth_count_sum_out, 0, (size_t)B * sizeof(int64_t));
-            if (stop_hist_out) memset(stop_hist_out, 0, (size_t)B * (N + 1) * sizeof(int64_t));
-            if (per_resample_out) memset(per_resample_out, 0, (size_t)(r_end - r_begin) * B * M * sizeof(int64_t));
-            return SCV_OK;
-        }
-        return adaptive_host(ctx, pool, tokens, cap, need, rule_flags, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
-                             tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, stop_hist_out, per_resample_out,
-                             cells_out, cell_tokens_out, cell_votes_out);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t), rules = (size_t)B * sizeof(int32_t);
+        enum { POOL, TOK, TRUTH, CAP, FLAGS, NEED, CELLS, CTOK, CVOTES, TIE, TSUM, VSUM, TCS, HIST, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(cap, rules), once_in(rule_flags, rules),
+                       once_in(need, rules * (N + 1)), rows_out(cells_out, (size_t)B * sizeof(scv_cell)), rows_out(cell_tokens_out, sums),
+                       rows_out(cell_votes_out, rules), sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums),
+                       sums_out(vote_count_sum_out, sums), sums_out(truth_count_sum_out, sums), sums_out(stop_hist_out, sums * (N + 1)),
+                       sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing voted, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {
+            return launch_adaptive(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[CAP].at<const int32_t>(),
+                                   rg[NEED].at<const int32_t>(), rg[FLAGS].at<const int32_t>(), rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0,
+                                   order, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(), rg[TSUM].at<int64_t>(), rg[VSUM].at<int64_t>(),
+                                   rg[TCS].at<int64_t>(), rg[HIST].at<int64_t>(), rg[PER].at<int64_t>(), rg[CELLS].at<scv_cell>(),
+                                   rg[CTOK].at<int64_t>(), rg[CVOTES].at<int32_t>(), err);
+        });
     });
 }
 
@@ -2295,7 +2104,13 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
         SCV_ENTER(ctx);
         if (mem_kind == SCV_MEM_DEVICE)
             return launch_expected(ctx, pool, n_valid, truth, P, B, N, expected_score_out, hit_prob_out, ctx->d_err);
-        return expected_host(ctx, pool, n_valid, truth, P, B, N, expected_score_out, hit_prob_out);
+        enum { POOL, TRUTH, NV, SCORE, HIT };
+        Region rg[] = {rows_in(pool, (size_t)N * sizeof(int32_t)), rows_in(truth, sizeof(int32_t)), once_in(n_valid, (size_t)B * sizeof(int32_t)),
+                       rows_out(expected_score_out, (size_t)B * sizeof(double)), rows_out(hit_prob_out, (size_t)B * sizeof(double))};
+        return stage_call(ctx, rg, HIT + 1, P, kStageChunkBytes, [&](int64_t np, int64_t, uint32_t* err) {
+            return launch_expected(ctx, rg[POOL].at<const int32_t>(), rg[NV].at<const int32_t>(), rg[TRUTH].at<const int32_t>(), np, B, N,
+                                   rg[SCORE].at<double>(), rg[HIT].at<double>(), err);
+        });
     });
 }
 

@@ -80,6 +80,43 @@ def _out(shape, dtype, written: bool):
     return np.empty(shape, dtype=dtype) if written else np.zeros(shape, dtype=dtype)
 
 
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _device_tensor(t, shape, name, dtype, dev, label=None, alloc=None, optional=False):
+    """A tensor of a DEVICE-mode call: contiguous, CUDA, of ``dtype`` and ``shape``, on ``dev`` (ValueError otherwise; ``label``: how the message
+    names the dtype, where that is not ``str(dtype)``).  None is replaced by ``alloc(shape, dtype=, device=)`` (torch.zeros / torch.empty) for an
+    output the caller left out, and stays None for an ``optional`` input."""
+    if t is None and alloc is not None:
+        return alloc(tuple(shape), dtype=dtype, device=dev)
+    if t is None and optional:
+        return None
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
+        raise ValueError(f"{name} must be a contiguous CUDA {label or dtype} tensor {tuple(shape)} on {dev}")
+    return t
+
+
+def _host_orderings(pool, tokens, resamples, r_begin, M, want_cells):
+    """Prologue of the HOST-mode *_prefix methods: pool (and tokens, when given) as contiguous int32 [P, N]; the orderings [r0, r1) -- ``resamples``
+    None: the pool's own order, one draw, the only one that writes cells --; ``M`` None: N + 1 classes.
+    Returns (pool, tokens, P, N, r0, r1, M, order)."""
+    pool = np.ascontiguousarray(pool, dtype=np.int32)
+    if pool.ndim != 2:
+        raise ValueError("pool must be [P, N]")
+    P, N = pool.shape
+    if tokens is not None:
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tokens.shape != pool.shape:
+            raise ValueError("tokens must match pool")
+    shuffled = resamples is not None
+    if want_cells and shuffled:
+        raise ValueError("cells are written in pool order only (resamples=None)")
+    r0 = int(r_begin)
+    r1 = r0 + (int(resamples) if shuffled else 1)
+    return pool, tokens, P, N, r0, r1, N + 1 if M is None else M, _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
+
+
 def pinned_empty(shape, dtype=np.int32) -> np.ndarray:
     """numpy array over page-locked host memory (scv_host_alloc): HOST-mode calls DMA such inputs in place instead
     of copying them through the pinned bounce slots first.  The memory is released when the array is collected."""
@@ -269,20 +306,13 @@ class Engine:
         resample.py).  pool int32 [P, N] (numpy, N <= 256), n_valid int32 [B] (B <= 32): budget b votes over the first n_valid[b]
         votes of each ordering r in [r_begin, r_begin + resamples).  Every denominator of the result is P * resamples.
         ``M``: classes of ``per_resample`` (None: max budget + 1, which no hit can exceed; 0: per_resample is not computed).  Blocking."""
-        pool = np.ascontiguousarray(pool, dtype=np.int32)
-        if pool.ndim != 2:
-            raise ValueError("pool must be [P, N]")
-        P, N = pool.shape
+        pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
         truth = np.ascontiguousarray(truth, dtype=np.int32)
         n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
         if truth.shape != (P,) or n_valid.ndim != 1:
             raise ValueError("truth must be [P] and n_valid [B]")
         B = n_valid.shape[0]
-        if tokens is not None:
-            tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-            if tokens.shape != pool.shape:
-                raise ValueError("tokens must match pool")
-        R = int(resamples)
+        R = r1 - r0
         if M is None:
             M = int(np.clip(n_valid, 0, N).max(initial=0)) + 1
         tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
@@ -290,7 +320,7 @@ class Engine:
         tcs = np.zeros((B,), dtype=np.int64)
         per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
         check(self._L.scv_resample_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth), P, B, N, p_offset,
-                                              r_begin, r_begin + R, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
+                                              r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
                                               _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
         return ResampleResult(P, R, tie, tok, tcs, per)
 
@@ -326,23 +356,14 @@ class Engine:
         ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells and cell tokens); otherwise the orderings
         r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of ``per_resample`` (None: N + 1, which no hit can exceed;
         0: not computed).  Blocking."""
-        pool = np.ascontiguousarray(pool, dtype=np.int32)
-        if pool.ndim != 2:
-            raise ValueError("pool must be [P, N]")
-        P, N = pool.shape
+        pool, _, P, N, r0, r1, M, order = _host_orderings(pool, None, resamples, r_begin, M, want_cells)
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         truth = np.ascontiguousarray(truth, dtype=np.int32)
         budgets = np.ascontiguousarray(token_budgets, dtype=np.int64)
         if tokens.shape != pool.shape or truth.shape != (P,) or budgets.ndim != 1:
             raise ValueError("tokens must match pool, truth must be [P] and token_budgets [B]")
         B = budgets.shape[0]
-        shuffled = resamples is not None
-        if want_cells and shuffled:
-            raise ValueError("cells are written in pool order only (resamples=None)")
-        r0, r1 = (int(r_begin), int(r_begin) + int(resamples)) if shuffled else (int(r_begin), int(r_begin) + 1)
         R = r1 - r0
-        if M is None:
-            M = N + 1
         tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
         tok = np.zeros((B,), dtype=np.int64)
         votes = np.zeros((B,), dtype=np.int64)
@@ -350,7 +371,6 @@ class Engine:
         per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
         cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
         cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
-        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
         check(self._L.scv_token_budget_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N,
                                                   p_offset, order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok),
                                                   _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
@@ -364,10 +384,7 @@ class Engine:
         ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells, whose max_count / truth_count carry weights);
         otherwise the orderings r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of ``per_resample`` (None: N + 1,
         which no hit can exceed; 0: not computed).  Blocking."""
-        pool = np.ascontiguousarray(pool, dtype=np.int32)
-        if pool.ndim != 2:
-            raise ValueError("pool must be [P, N]")
-        P, N = pool.shape
+        pool, tokens, P, N, r0, r1, M, order = _host_orderings(pool, tokens, resamples, r_begin, M, want_cells)
         if weights is None:
             raise ValueError("weights are required")
         weights = np.ascontiguousarray(weights, dtype=np.int32)
@@ -376,23 +393,12 @@ class Engine:
         if weights.shape != pool.shape or truth.shape != (P,) or n_valid.ndim != 1:
             raise ValueError("weights must match pool, truth must be [P] and n_valid [B]")
         B = n_valid.shape[0]
-        if tokens is not None:
-            tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-            if tokens.shape != pool.shape:
-                raise ValueError("tokens must match pool")
-        shuffled = resamples is not None
-        if want_cells and shuffled:
-            raise ValueError("cells are written in pool order only (resamples=None)")
-        r0, r1 = (int(r_begin), int(r_begin) + int(resamples)) if shuffled else (int(r_begin), int(r_begin) + 1)
         R = r1 - r0
-        if M is None:
-            M = N + 1
         tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
         tok = np.zeros((B,), dtype=np.int64) if tokens is not None else None
         per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
         cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
         cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells and tokens is not None else None
-        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
         check(self._L.scv_weighted_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(weights), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth),
                                               P, B, N, p_offset, int(rule), order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
                                               _np_ptr(tok), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
@@ -406,26 +412,13 @@ class Engine:
         (STOP_DECIDED), tokens [P, N] or None.  ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells, cell
         tokens and cell votes); otherwise the orderings r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of
         ``per_resample`` (None: N + 1, which no hit can exceed; 0: not computed).  Blocking."""
-        pool = np.ascontiguousarray(pool, dtype=np.int32)
-        if pool.ndim != 2:
-            raise ValueError("pool must be [P, N]")
-        P, N = pool.shape
+        pool, tokens, P, N, r0, r1, M, order = _host_orderings(pool, tokens, resamples, r_begin, M, want_cells)
         truth = np.ascontiguousarray(truth, dtype=np.int32)
         if truth.shape != (P,):
             raise ValueError("truth must be [P]")
         cap, need, flags = check_rules(cap, need, rule_flags, N)
         B = cap.shape[0]
-        if tokens is not None:
-            tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-            if tokens.shape != pool.shape:
-                raise ValueError("tokens must match pool")
-        shuffled = resamples is not None
-        if want_cells and shuffled:
-            raise ValueError("cells are written in pool order only (resamples=None)")
-        r0, r1 = (int(r_begin), int(r_begin) + int(resamples)) if shuffled else (int(r_begin), int(r_begin) + 1)
         R = r1 - r0
-        if M is None:
-            M = N + 1
         tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
         tok = np.zeros((B,), dtype=np.int64) if tokens is not None else None
         votes = np.zeros((B,), dtype=np.int64)
@@ -435,7 +428,6 @@ class Engine:
         cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
         cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells and tokens is not None else None
         cell_votes = np.zeros((P, B), dtype=np.int32) if want_cells else None
-        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
         check(self._L.scv_adaptive_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(cap), _np_ptr(need),
                                               _np_ptr(flags) if rule_flags is not None else None, _np_ptr(truth), P, B, N, p_offset, order,
                                               r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok), _np_ptr(votes),
@@ -481,9 +473,8 @@ class Engine:
             check(self._L.scv_set_option(self._ctx, b"overwrite_counters", int(bool(overwrite))))
             self._overwrite = bool(overwrite)
         base = counters.data_ptr()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         cptrs = (C.c_void_p(base), C.c_void_p(base + 8 * B * TIE_CLASSES), C.c_void_p(base + 8 * (B * TIE_CLASSES + B)))
-        return P, B, N, counters, cells, cell_tokens, ptr, cptrs
+        return P, B, N, counters, cells, cell_tokens, _ptr, cptrs
 
     def aggregate_device(self, answers, truth, tokens=None, n_valid=None, counters=None, cells=None,
                          cell_tokens=None, overwrite=False):
@@ -541,8 +532,7 @@ class Engine:
     def synth_fill_device(self, answers=None, tokens=None, truth=None, *, P, B, N, seed, dist, p_offset=0):
         """Fill preallocated CUDA int32 tensors with the closed-form synthetic data (asynchronous)."""
         self.use_torch_stream()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        check(self._L.scv_synth_fill_i32(self._ctx, ptr(answers), ptr(tokens), ptr(truth), P, B, N, p_offset, seed, dist))
+        check(self._L.scv_synth_fill_i32(self._ctx, _ptr(answers), _ptr(tokens), _ptr(truth), P, B, N, p_offset, seed, dist))
 
     def export_error_word(self, dst):
         """dst: int64 cuda tensor (>= 1 element, on the engine's device).  dst[0] = the device error word, written in
@@ -567,6 +557,33 @@ class Engine:
                                     _lib.MEM_DEVICE, C.c_void_p(out.data_ptr())))
         return out
 
+    def _lane_device(self, pool, B, inputs, r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", None)):
+        """Prologue of the four *_prefix_device methods.  Checks ``pool`` (contiguous CUDA int32 [P, N] on the engine's device) and ``inputs`` --
+        (name, tensor, shape, dtype, optional) with shape "P", "PN", "B" or "BN1" ([B, N + 1]) --, derives the orderings (``r_end`` None: the
+        pool's own order, one draw), checks or allocates zeroed tie_class_hits and -- when ``M`` or the buffer is given -- per_resample, and binds
+        torch's current stream.  ``labels``: how the messages about inputs / int64 outputs name the dtype, where not ``str(dtype)``.
+        Returns (P, N, device, r_end, order, tie_class_hits, per_resample, M)."""
+        import torch
+        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
+            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
+        self._check_device(pool, "pool")
+        P, N = int(pool.shape[0]), int(pool.shape[1])
+        dev = pool.device
+        shapes = {"P": (P,), "PN": (P, N), "B": (B,), "BN1": (B, N + 1)}
+        for name, t, shape, dtype, optional in inputs:
+            _device_tensor(t, shapes[shape], name, dtype, dev, labels[0], optional=optional)
+        shuffled = r_end is not None
+        if not shuffled:
+            r_end = int(r_begin) + 1
+        R = int(r_end) - int(r_begin)
+        tie_class_hits = _device_tensor(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits", torch.int64, dev, labels[1], torch.zeros)
+        if per_resample is not None and M is None:
+            M = int(per_resample.shape[2])
+        if M is not None:
+            per_resample = _device_tensor(per_resample, (max(R, 0), B, M), "per_resample", torch.int64, dev, labels[1], torch.zeros)
+        self.use_torch_stream()
+        return P, N, dev, r_end, _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL, tie_class_hits, per_resample, M
+
     def resample_prefix_device(self, pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
                                tie_class_hits=None, token_sum=None, truth_count_sum=None, per_resample=None, M: int | None = None):
         """DEVICE-mode resample_prefix: pool / tokens torch.int32 cuda [P, N], n_valid [B], truth [P].  ACCUMULATES into the given
@@ -574,37 +591,16 @@ class Engine:
         None are allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise
         (a hit with n_modes >= M is reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
         import torch
-        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
-            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
-        self._check_device(pool, "pool")
-        P, N = int(pool.shape[0]), int(pool.shape[1])
-        dev = pool.device
+        i32 = torch.int32
         B = int(n_valid.shape[0])
-        for name, t, shape in (("truth", truth, (P,)), ("tokens", tokens, (P, N)), ("n_valid", n_valid, (B,))):
-            if t is None:
-                continue
-            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
-        R = int(r_end) - int(r_begin)
-
-        def buf(t, shape, name):
-            if t is None:
-                return torch.zeros(shape, dtype=torch.int64, device=dev)
-            if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA int64 tensor {tuple(shape)} on {dev}")
-            return t
-        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
-        token_sum = buf(token_sum, (B,), "token_sum") if tokens is not None else None
-        truth_count_sum = buf(truth_count_sum, (B,), "truth_count_sum")
-        if per_resample is not None and M is None:
-            M = int(per_resample.shape[2])
-        if M is not None:
-            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
-        self.use_torch_stream()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        check(self._L.scv_resample_prefix_i32(self._ctx, ptr(pool), ptr(tokens), ptr(n_valid), ptr(truth), P, B, N, p_offset, r_begin, r_end,
-                                              seed, M if M is not None else 1, _lib.MEM_DEVICE, ptr(tie_class_hits), ptr(token_sum),
-                                              ptr(truth_count_sum), ptr(per_resample)))
+        P, N, dev, _, _, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("truth", truth, "P", i32, True), ("tokens", tokens, "PN", i32, True), ("n_valid", n_valid, "B", i32, True)),
+            r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", "int64"))
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", torch.int64, dev, "int64", torch.zeros) if tokens is not None else None
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", torch.int64, dev, "int64", torch.zeros)
+        check(self._L.scv_resample_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_valid), _ptr(truth), P, B, N, p_offset, r_begin, r_end,
+                                              seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum),
+                                              _ptr(truth_count_sum), _ptr(per_resample)))
         return tie_class_hits, token_sum, truth_count_sum, per_resample
 
     def expected_majority_device(self, pool, truth, n_valid, score=None, hit_prob=None, want_hit_prob: bool = True):
@@ -618,23 +614,14 @@ class Engine:
         P, N = int(pool.shape[0]), int(pool.shape[1])
         dev = pool.device
         B = int(n_valid.shape[0])
-        for name, t, shape in (("truth", truth, (P,)), ("n_valid", n_valid, (B,))):
-            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
-
-        def buf(t, name):
-            if t is None:
-                return torch.empty((P, B), dtype=torch.float64, device=dev)
-            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (P, B) and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA float64 tensor {(P, B)} on {dev}")
-            return t
-        score = buf(score, "score")
+        _device_tensor(truth, (P,), "truth", torch.int32, dev, "int32")
+        _device_tensor(n_valid, (B,), "n_valid", torch.int32, dev, "int32")
+        score = _device_tensor(score, (P, B), "score", torch.float64, dev, "float64", torch.empty)
         if hit_prob is not None or want_hit_prob:
-            hit_prob = buf(hit_prob, "hit_prob")
+            hit_prob = _device_tensor(hit_prob, (P, B), "hit_prob", torch.float64, dev, "float64", torch.empty)
         self.use_torch_stream()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        check(self._L.scv_expected_majority_i32(self._ctx, ptr(pool), ptr(n_valid), ptr(truth), P, B, N, _lib.MEM_DEVICE, ptr(score),
-                                                ptr(hit_prob)))
+        check(self._L.scv_expected_majority_i32(self._ctx, _ptr(pool), _ptr(n_valid), _ptr(truth), P, B, N, _lib.MEM_DEVICE, _ptr(score),
+                                                _ptr(hit_prob)))
         return score, hit_prob
 
 
@@ -648,46 +635,22 @@ class Engine:
         (int64 [P, B]), allocated when ``want_cells``.  Runs on torch's current stream, does not synchronise.  Returns (tie_class_hits,
         token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens)."""
         import torch
-        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
-            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
-        self._check_device(pool, "pool")
-        P, N = int(pool.shape[0]), int(pool.shape[1])
-        dev = pool.device
+        i32, i64 = torch.int32, torch.int64
         B = int(token_budgets.shape[0])
-        for name, t, shape, dt in (("tokens", tokens, (P, N), torch.int32), ("truth", truth, (P,), torch.int32),
-                                   ("token_budgets", token_budgets, (B,), torch.int64)):
-            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {shape} on {dev}")
-        shuffled = r_end is not None
-        if not shuffled:
-            r_end = int(r_begin) + 1
-        R = int(r_end) - int(r_begin)
-
-        def buf(t, shape, name, dt=torch.int64):
-            if t is None:
-                return torch.zeros(shape, dtype=dt, device=dev)
-            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {tuple(shape)} on {dev}")
-            return t
-        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
-        token_sum = buf(token_sum, (B,), "token_sum")
-        vote_count_sum = buf(vote_count_sum, (B,), "vote_count_sum")
-        truth_count_sum = buf(truth_count_sum, (B,), "truth_count_sum")
-        if per_resample is not None and M is None:
-            M = int(per_resample.shape[2])
-        if M is not None:
-            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        P, N, dev, r_end, order, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("tokens", tokens, "PN", i32, False), ("truth", truth, "P", i32, False), ("token_budgets", token_budgets, "B", i64, False)),
+            r_begin, r_end, tie_class_hits, per_resample, M, labels=(None, None))
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", i64, dev, alloc=torch.zeros)
+        vote_count_sum = _device_tensor(vote_count_sum, (B,), "vote_count_sum", i64, dev, alloc=torch.zeros)
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", i64, dev, alloc=torch.zeros)
         if want_cells or cells is not None:
-            cells = buf(cells, (P, B, 16), "cells", torch.uint8)
+            cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
         if want_cells or cell_tokens is not None:
-            cell_tokens = buf(cell_tokens, (P, B), "cell_tokens")
-        self.use_torch_stream()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
-        check(self._L.scv_token_budget_prefix_i32(self._ctx, ptr(pool), ptr(tokens), ptr(token_budgets), ptr(truth), P, B, N, p_offset, order,
-                                                  r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, ptr(tie_class_hits),
-                                                  ptr(token_sum), ptr(vote_count_sum), ptr(truth_count_sum), ptr(per_resample), ptr(cells),
-                                                  ptr(cell_tokens)))
+            cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
+        check(self._L.scv_token_budget_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(token_budgets), _ptr(truth), P, B, N, p_offset, order,
+                                                  r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits),
+                                                  _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(per_resample), _ptr(cells),
+                                                  _ptr(cell_tokens)))
         return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
 
     def weighted_prefix_device(self, pool, weights, truth, n_valid, rule: int = _lib.RULE_WEIGHT_SUM, r_begin: int = 0, r_end: int | None = None,
@@ -700,46 +663,21 @@ class Engine:
         allocated when ``want_cells``.  One launch on torch's current stream, does not synchronise (a weight out of range is reported by
         ``sync``).  Returns (tie_class_hits, token_sum, per_resample, cells, cell_tokens)."""
         import torch
-        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
-            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
-        self._check_device(pool, "pool")
-        P, N = int(pool.shape[0]), int(pool.shape[1])
-        dev = pool.device
+        i32, i64 = torch.int32, torch.int64
         if weights is None:
             raise ValueError("weights are required")
         B = int(n_valid.shape[0])
-        for name, t, shape in (("weights", weights, (P, N)), ("tokens", tokens, (P, N)), ("truth", truth, (P,)), ("n_valid", n_valid, (B,))):
-            if t is None and name == "tokens":
-                continue
-            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
-        shuffled = r_end is not None
-        if not shuffled:
-            r_end = int(r_begin) + 1
-        R = int(r_end) - int(r_begin)
-
-        def buf(t, shape, name, dt=torch.int64):
-            if t is None:
-                return torch.zeros(shape, dtype=dt, device=dev)
-            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {tuple(shape)} on {dev}")
-            return t
-        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
-        token_sum = buf(token_sum, (B,), "token_sum") if tokens is not None else None
-        if per_resample is not None and M is None:
-            M = int(per_resample.shape[2])
-        if M is not None:
-            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        P, N, dev, r_end, order, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("weights", weights, "PN", i32, False), ("tokens", tokens, "PN", i32, True), ("truth", truth, "P", i32, False),
+                      ("n_valid", n_valid, "B", i32, False)), r_begin, r_end, tie_class_hits, per_resample, M)
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", i64, dev, alloc=torch.zeros) if tokens is not None else None
         if want_cells or cells is not None:
-            cells = buf(cells, (P, B, 16), "cells", torch.uint8)
+            cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
         if (want_cells and tokens is not None) or cell_tokens is not None:
-            cell_tokens = buf(cell_tokens, (P, B), "cell_tokens")
-        self.use_torch_stream()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
-        check(self._L.scv_weighted_prefix_i32(self._ctx, ptr(pool), ptr(weights), ptr(tokens), ptr(n_valid), ptr(truth), P, B, N, p_offset,
+            cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
+        check(self._L.scv_weighted_prefix_i32(self._ctx, _ptr(pool), _ptr(weights), _ptr(tokens), _ptr(n_valid), _ptr(truth), P, B, N, p_offset,
                                               int(rule), order, r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE,
-                                              ptr(tie_class_hits), ptr(token_sum), ptr(per_resample), ptr(cells), ptr(cell_tokens)))
+                                              _ptr(tie_class_hits), _ptr(token_sum), _ptr(per_resample), _ptr(cells), _ptr(cell_tokens)))
         return tie_class_hits, token_sum, per_resample, cells, cell_tokens
 
     def adaptive_prefix_device(self, pool, truth, cap, need, rule_flags=None, tokens=None, r_begin: int = 0, r_end: int | None = None,
@@ -755,51 +693,26 @@ class Engine:
         ``sync``).  Returns (tie_class_hits, token_sum, vote_count_sum, truth_count_sum, stop_hist, per_resample, cells, cell_tokens,
         cell_votes)."""
         import torch
-        if not (pool.is_cuda and pool.dtype == torch.int32 and pool.is_contiguous() and pool.dim() == 2):
-            raise ValueError("pool must be a contiguous CUDA int32 tensor [P, N]")
-        self._check_device(pool, "pool")
-        P, N = int(pool.shape[0]), int(pool.shape[1])
-        dev = pool.device
+        i32, i64 = torch.int32, torch.int64
         B = int(cap.shape[0])
-        for name, t, shape in (("tokens", tokens, (P, N)), ("truth", truth, (P,)), ("cap", cap, (B,)), ("need", need, (B, N + 1)),
-                               ("rule_flags", rule_flags, (B,))):
-            if t is None and name in ("tokens", "rule_flags"):
-                continue
-            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA int32 tensor {shape} on {dev}")
-        shuffled = r_end is not None
-        if not shuffled:
-            r_end = int(r_begin) + 1
-        R = int(r_end) - int(r_begin)
-
-        def buf(t, shape, name, dt=torch.int64):
-            if t is None:
-                return torch.zeros(shape, dtype=dt, device=dev)
-            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
-                raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor {tuple(shape)} on {dev}")
-            return t
-        tie_class_hits = buf(tie_class_hits, (B, TIE_CLASSES), "tie_class_hits")
-        token_sum = buf(token_sum, (B,), "token_sum") if tokens is not None else None
-        vote_count_sum = buf(vote_count_sum, (B,), "vote_count_sum")
-        truth_count_sum = buf(truth_count_sum, (B,), "truth_count_sum")
-        stop_hist = buf(stop_hist, (B, N + 1), "stop_hist")
-        if per_resample is not None and M is None:
-            M = int(per_resample.shape[2])
-        if M is not None:
-            per_resample = buf(per_resample, (max(R, 0), B, M), "per_resample")
+        P, N, dev, r_end, order, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("tokens", tokens, "PN", i32, True), ("truth", truth, "P", i32, False), ("cap", cap, "B", i32, False),
+                      ("need", need, "BN1", i32, False), ("rule_flags", rule_flags, "B", i32, True)),
+            r_begin, r_end, tie_class_hits, per_resample, M)
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", i64, dev, alloc=torch.zeros) if tokens is not None else None
+        vote_count_sum = _device_tensor(vote_count_sum, (B,), "vote_count_sum", i64, dev, alloc=torch.zeros)
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", i64, dev, alloc=torch.zeros)
+        stop_hist = _device_tensor(stop_hist, (B, N + 1), "stop_hist", i64, dev, alloc=torch.zeros)
         if want_cells or cells is not None:
-            cells = buf(cells, (P, B, 16), "cells", torch.uint8)
+            cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
         if (want_cells and tokens is not None) or cell_tokens is not None:
-            cell_tokens = buf(cell_tokens, (P, B), "cell_tokens")
+            cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
         if want_cells or cell_votes is not None:
-            cell_votes = buf(cell_votes, (P, B), "cell_votes", torch.int32)
-        self.use_torch_stream()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        order = _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL
-        check(self._L.scv_adaptive_prefix_i32(self._ctx, ptr(pool), ptr(tokens), ptr(cap), ptr(need), ptr(rule_flags), ptr(truth), P, B, N,
+            cell_votes = _device_tensor(cell_votes, (P, B), "cell_votes", i32, dev, alloc=torch.zeros)
+        check(self._L.scv_adaptive_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(cap), _ptr(need), _ptr(rule_flags), _ptr(truth), P, B, N,
                                               p_offset, order, r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE,
-                                              ptr(tie_class_hits), ptr(token_sum), ptr(vote_count_sum), ptr(truth_count_sum), ptr(stop_hist),
-                                              ptr(per_resample), ptr(cells), ptr(cell_tokens), ptr(cell_votes)))
+                                              _ptr(tie_class_hits), _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(stop_hist),
+                                              _ptr(per_resample), _ptr(cells), _ptr(cell_tokens), _ptr(cell_votes)))
         return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, stop_hist, per_resample, cells, cell_tokens, cell_votes
 
 
