@@ -1,7 +1,10 @@
 """GPU tests of scv_adaptive_prefix_i32 (the majority vote that samples until a stopping rule says it is settled): every output bit-exact
 against the CPU mirror (o1_inference_scaling_laws_amd/adaptive.py) in both orders, the reductions to the live scv_resample_prefix_i32 /
 scv_aggregate_prefix_i32 under `never`, edges (caps of 0 and beyond N, 32 identical rules, 256 equal or distinct votes, grids, a two-chunk
-HOST call), HOST against DEVICE, slices and shards, a captured graph, the clamp flag and the errors."""
+HOST call, more than 2^32 stops through one workgroup's tie and stop tables), HOST against DEVICE, slices and shards, a captured graph, the
+clamp flag and the errors."""
+import time
+
 import numpy as np
 import pytest
 
@@ -231,6 +234,32 @@ def test_host_staging_chunks_match_one_device_launch(hip_engine):
     bad[29_000, 3] = -4                                                 # only the second chunk holds it
     with pytest.raises(_lib.DomainError):
         hip_engine.adaptive_prefix(bad, tr, cap, need, flags, tokens=tok)
+
+
+def test_tie_and_stop_counters_do_not_wrap(hip_engine, grid_option):
+    """One workgroup, 3 (2^31 - 1) lanes; each stops rule 1 (cap 0) at n = 0 and rule 0 (cap 1, `never`) at n = 1 with a hit of one mode:
+    one tie counter and two stop counters take 3 R > 2^32 increments, and a 32-bit LDS counter would wrap to 2^31 - 3.  The expected values
+    are worked out by hand: the mirror cannot run 6.4e9 orderings."""
+    R = 2 ** 31 - 1
+    pool = np.full((3, 1), 4, dtype=np.int32)
+    tok = np.ones((3, 1), dtype=np.int32)
+    tr = np.full(3, 4, dtype=np.int32)
+    cap = np.array([1, 0], dtype=np.int32)
+    need = np.tile(never(1), (2, 1))
+    grid_option(1)
+    t0 = time.perf_counter()
+    dp, dt, dtr, dc, dn = to_dev(pool, tok, tr, cap, need)
+    tie, ts, vs, tcs, hist, per, _, _, _ = hip_engine.adaptive_prefix_device(dp, dtr, dc, dn, None, tokens=dt, r_begin=0, r_end=R, seed=5)
+    hip_engine.sync()
+    print(f"\nadaptive overflow test: {time.perf_counter() - t0:.1f} s")
+    tie, hist = tie.cpu().numpy(), hist.cpu().numpy()
+    assert per is None
+    assert int(tie[0, 1]) == 3 * R and int(tie[0].sum()) == 3 * R and int(tie[1].sum()) == 0
+    want_hist = np.zeros((2, 2), dtype=np.int64)
+    want_hist[0, 1] = want_hist[1, 0] = 3 * R
+    assert np.array_equal(hist, want_hist)
+    for s in (vs, tcs, ts):
+        assert s.cpu().numpy().tolist() == [3 * R, 0]
 
 
 def test_slices_and_shards_add_up_on_the_device(hip_engine):
