@@ -435,6 +435,46 @@ int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
                             int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out, int32_t* cell_votes_out);
 
 /*
+ * Majority vote over draws WITH replacement, past the size of the pool: the plug-in (bootstrap) estimate of maj@k (new semantics, not in
+ * the reference, whose curve ends at its largest pool, 128 samples, o1.py:266-276).  A problem's pool is taken for the model's answer
+ * distribution; k answers are drawn from it with replacement and voted on.  This is defined for any k and smooth in k; its limit as k grows
+ * is the score of the vote over the whole pool (scv_aggregate_prefix_i32 at k = N).
+ *   pool / tokens  int32 [P, N] (tokens may be NULL); truth int32 [P]; n_draws int32 [B] (required, any order, duplicates fine)
+ * The budget is k_b = max(n_draws[b], 0).  It is NOT clamped to N.  The limit is k_b <= SCV_IID_MAX_DRAWS = 65535, so a count fits 16 bits.
+ * For problem p (global index pg = p_offset + p) and resample r in [r_begin, r_end):
+ *   s      = mix64((seed ^ 0xA0761D6478BD642F) + G * (pg + 1))                       (uint64, wrapping; mix64, G, mulhi32 as above)
+ *            The salt differs from scv_resample_prefix_i32's, so this call's draws are independent of that call's for the same seed.
+ *   draw i = 0, 1, ...:  u = mix64(s + G * ((uint64)r * 65536 + i + 1)),  x_i = pool[p, mulhi32(hi32(u), N)]
+ *            The stride per resample is 65536 > SCV_IID_MAX_DRAWS, so the streams of different r never overlap.
+ *   cell (p, r, b) = statistics.multimode(x_0 ... x_{k_b - 1}), scored as everywhere else (1 / n_modes on a hit); k = 0 is the empty cell
+ *            (no hit).  The budgets of one resample are nested prefixes of one draw sequence.
+ * Votes, truths and the clamp flag follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in
+ * HOST mode, at scv_sync in DEVICE mode) or counts in bin 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Outputs and their accumulation rules are those of scv_resample_prefix_i32, summed over the P x (r_end - r_begin) cells of a budget:
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational);
+ *                        n_modes <= min(distinct values, k) <= N, so the table keeps its shape for k > N
+ *   token_sum_out        int64 [B]        (NULL ok; requires tokens) tokens of the draws (a sample drawn twice is paid twice)
+ *   truth_count_sum_out  int64 [B]        (NULL ok) draws equal to the truth
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) class counts per resample, summed over problems only (m < M; a hit with
+ *                        n_modes >= M sets error bit 1: SCV_ERR_ARG at scv_sync)
+ * DEVICE mode ACCUMULATES into every output (+=) and only enqueues: no allocation, no synchronisation, legal under hipGraph capture.
+ * HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices of r and shards of p (p_offset) add up to the
+ * whole call bit for bit.  Limits: 1 <= N <= 256, 1 <= B <= 32, 0 <= r_begin <= r_end < 2^31, p_offset >= 0, M >= 1 when per_resample_out
+ * is given, token_sum_out only with tokens; anything else is SCV_ERR_ARG.  A budget k_b > SCV_IID_MAX_DRAWS is SCV_ERR_ARG at the call in
+ * HOST mode; in DEVICE mode the kernel raises error bit 7 and computes nothing for that call (SCV_ERR_ARG at scv_sync, outputs untouched).
+ * One lane per (problem, resample), P * R * max_b k_b steps of one draw, one 16-bit count in LDS and one running-mode update
+ * (csrc/scvote_iid.hip.h); the pool is read once.
+ */
+#define SCV_IID_MAX_DRAWS 65535
+int scv_iid_prefix_i32(scv_ctx* ctx,
+                       const int32_t* pool, const int32_t* tokens,
+                       const int32_t* n_draws, const int32_t* truth,
+                       int64_t P, int32_t B, int64_t N, int64_t p_offset,
+                       int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                       int64_t* tie_class_hits_out, int64_t* token_sum_out,
+                       int64_t* truth_count_sum_out, int64_t* per_resample_out);
+
+/*
  * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
  * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
  * seed and nothing left to converge.
@@ -463,7 +503,7 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
 
 /*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 7: a draw budget above SCV_IID_MAX_DRAWS in a DEVICE-mode scv_iid_prefix_i32, which then computed nothing; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the

@@ -1078,6 +1078,7 @@ int check_err_word(scv_ctx* ctx, uint32_t w) {
     if (w & 16u) return fail(SCV_ERR_ARG, "token_budget: a token count was negative; results are invalid");
     if (w & 32u) return fail(SCV_ERR_ARG, "weighted: a weight was outside 0..%d; results are invalid", SCV_WEIGHT_MAX);
     if (w & 64u) return fail(SCV_ERR_ARG, "adaptive: a rule flag had a bit other than SCV_STOP_DECIDED; results are invalid");
+    if (w & 128u) return fail(SCV_ERR_ARG, "iid: a draw budget was above SCV_IID_MAX_DRAWS = %d; nothing was computed", SCV_IID_MAX_DRAWS);
     if (w & 8u) return fail(SCV_ERR_ARG, "prefix_path = 5 promised budgets that are 0, a power of two or >= N: the list in n_valid is not; nothing was computed");
     return SCV_OK;
 }
@@ -1671,7 +1672,21 @@ int launch_adaptive(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, co
                             [&](int lanes, int np) { return scv::adaptive_lds_words((int)N, B, lanes, np, shuffled); }, "adaptive", nullptr);
 }
 
-// The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32 and scv_adaptive_prefix_i32 share, in
+// scv_iid_prefix_i32 on device pointers: one launch of the draws-with-replacement body of scv_resample_prefix<false> (scvote_iid.hip.h),
+// accumulating into the outputs.
+int launch_iid(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_draws, const int32_t* truth,
+               int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+               int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    scv::ResampleArgs a = lane_args(pool, tokens, n_draws, truth, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, seed, M, tie, tok_sum,
+                                    truth_sum, per_resample, err);
+    a.mode = scv::kResampleModeIid;
+    return launch_lane_body(ctx, pick_resample_kernel(false), a,
+                            [&](int lanes, int np) { return scv::iid_lds_words((int)N, B, lanes, np); }, "iid", nullptr);
+}
+
+// The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32, scv_adaptive_prefix_i32 and
+// scv_iid_prefix_i32 share, in
 // the order the entries have always made them; `what` names the entry in every message.  An entry's own checks keep their places in that
 // order: `early` runs behind the shape check (weighted: the rule), `own` behind the P * R bound (the pointers the entry requires).
 // cells_given: the cell outputs of the entry as its message lists them when the caller passed one, NULL when it passed none.
@@ -2086,6 +2101,39 @@ int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
                                    order, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(), rg[TSUM].at<int64_t>(), rg[VSUM].at<int64_t>(),
                                    rg[TCS].at<int64_t>(), rg[HIST].at<int64_t>(), rg[PER].at<int64_t>(), rg[CELLS].at<scv_cell>(),
                                    rg[CTOK].at<int64_t>(), rg[CVOTES].at<int32_t>(), err);
+        });
+    });
+}
+
+int scv_iid_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_draws, const int32_t* truth,
+                       int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                       int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* truth_count_sum_out,
+                       int64_t* per_resample_out) {
+    return guarded([&]() -> int {
+        if (int rc = check_lane_call("iid", ctx, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, nullptr, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!n_draws || !tie_class_hits_out) return fail(SCV_ERR_ARG, "iid: n_draws and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "iid: pool and truth are required");
+                if (token_sum_out && !tokens) return fail(SCV_ERR_ARG, "iid: token_sum_out needs tokens");
+                return SCV_OK;
+            })) return rc;
+        if (mem_kind == SCV_MEM_HOST)                                              // (DEVICE mode: the kernel checks, error bit 7 at scv_sync)
+            for (int32_t b = 0; b < B; ++b)
+                if (n_draws[b] > SCV_IID_MAX_DRAWS) return fail(SCV_ERR_ARG, "iid: n_draws[%d] = %d is above SCV_IID_MAX_DRAWS = %d", b, n_draws[b], SCV_IID_MAX_DRAWS);
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_iid(ctx, pool, tokens, n_draws, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out, token_sum_out,
+                              truth_count_sum_out, per_resample_out, ctx->d_err);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t);
+        enum { POOL, TOK, TRUTH, ND, TIE, TSUM, TCS, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(n_draws, (size_t)B * sizeof(int32_t)),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums), sums_out(truth_count_sum_out, sums),
+                       sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing drawn, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {
+            return launch_iid(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[ND].at<const int32_t>(),
+                              rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
+                              rg[TSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(), err);
         });
     });
 }

@@ -95,10 +95,12 @@ struct ResampleArgs {
     const int32_t* rule_flags;                           // [B] (NULL: all 0) bit 0: SCV_STOP_DECIDED
     unsigned long long* stop_hist;                       // [B, N + 1] cells that stopped after n samples (NULL ok)
     int32_t* cell_votes_out;                             // [P, B] (NULL ok; pool order only), overwritten
+    // the vote over draws with replacement (scv_iid_prefix_i32, scvote_iid.hip.h) adds no field: n_valid holds the draw budgets (not clamped
+    // to N), tokens may be NULL
 };
 using ResampleFn = void (*)(const ResampleArgs);
 constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3,
-                  kResampleModeAdaptive = 4;
+                  kResampleModeAdaptive = 4, kResampleModeIid = 5;
 constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
 // LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
 // budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
@@ -113,6 +115,12 @@ constexpr long long token_budget_lds_words(int N, int B, int lanes, int np_max, 
 constexpr long long adaptive_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
     return 6LL * B + 32 + 2 + 2LL * B * (N + 1) + ((long long)B * (N + 1) + 1) / 2 + 64LL * (lanes / 64) + 2LL * np_max +
            (long long)np_max * ((N + 3) / 4) + (shuffled ? 2LL : 1LL) * lanes * ((N + 3) / 4);
+}
+// LDS words of a workgroup of the vote over draws with replacement (scvote_iid.hip.h, in this order): per-budget sums (2 B int64) | tie classes
+// [B][N + 1] | sorted budgets and their order (2 x 32) | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
+// the rows as byte codes [np_max][N4] | the lanes' 16-bit counts, two per word [(N + 1) / 2][lanes]
+constexpr long long iid_lds_words(int N, int B, int lanes, int np_max) {
+    return 4LL * B + (long long)B * (N + 1) + 64 + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) + (long long)lanes * ((N + 1) / 2);
 }
 // The weighted body stages a row as N words (code | weight << 8) when a chunk of lanes touches few rows, R >= kWeightedLdsRowsMinR (at most
 // lanes / R + 2 rows); below that -- and in pool order, R = 1 -- as byte codes, with the weight read from global memory: lanes + 1 rows of N words

@@ -29,8 +29,9 @@
 //    no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
 //
 // LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
-// The <false> instantiation has two more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h)
-// and the weighted vote / best-of-N (mode kResampleModeWeighted, scvote_weighted.hip.h); the <true> one the vote over the longest prefix
+// The <false> instantiation has three more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h),
+// the weighted vote / best-of-N (mode kResampleModeWeighted, scvote_weighted.hip.h) and the vote over draws with replacement (mode
+// kResampleModeIid, scvote_iid.hip.h); the <true> one the vote over the longest prefix
 // that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h) and the vote that stops by a rule on its own state
 // (mode kResampleModeAdaptive, scvote_adaptive.hip.h).
 #pragma once
@@ -107,6 +108,7 @@ __device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64
 #include "scvote_budget.hip.h"
 #include "scvote_weighted.hip.h"
 #include "scvote_adaptive.hip.h"
+#include "scvote_iid.hip.h"
 
 namespace scv {
 
@@ -116,6 +118,7 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
     if constexpr (!TOK) {
         if (a.mode == kResampleModeExpected) { expected_majority_body(a, smem_wg); return; }    // the exact form: scvote_expected.hip.h
         if (a.mode == kResampleModeWeighted) { weighted_body(a, smem_wg); return; }             // weighted vote / best-of-N: scvote_weighted.hip.h
+        if (a.mode == kResampleModeIid) { iid_body(a, smem_wg); return; }                       // draws with replacement: scvote_iid.hip.h
     } else {
         if (a.mode == kResampleModeTokenBudget) { token_budget_body(a, smem_wg); return; }      // token budgets: scvote_budget.hip.h
         if (a.mode == kResampleModeAdaptive) { adaptive_body(a, smem_wg); return; }             // stopping rules: scvote_adaptive.hip.h

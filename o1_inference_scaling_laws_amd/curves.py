@@ -6,7 +6,8 @@ is one ordering of the cache.  ``expected_majority_records`` averages each point
 pool and returns it in the reference's log schema, so plot_helpers can draw the smoothed tail next to the single-ordering one.
 ``exact_majority_records`` gives the limit of that average -- the mean over all k-subsets -- with no seed and no resample count.
 ``token_budget_records`` ends each vote where a budget of TOKENS runs out instead of after a number of samples;
-``adaptive_vote_records`` where a stopping rule on the vote's own state says it is settled."""
+``adaptive_vote_records`` where a stopping rule on the vote's own state says it is settled.  ``iid_majority_records`` draws WITH
+replacement, so its curve goes on past the size of the pool, and ends in the k -> infinity limit."""
 from __future__ import annotations
 
 import numpy as np
@@ -102,3 +103,31 @@ def adaptive_vote_records(engine, pool, truth, tokens, rules, resamples: int | N
     res = engine.adaptive_prefix(pool, truth, cap, need, flags, tokens=tokens, resamples=resamples, seed=seed, M=0)
     return [{"rule": b, "accuracy": res.accuracy(b), "avg_votes": float(res.avg_votes(b)),
              "avg_tokens_used": float(res.avg_tokens_used(b)) if tokens is not None else 0.0} for b in range(len(rules))]
+
+
+def iid_majority_records(engine, pool, truth, tokens, draws, resamples: int, seed: int, token_limits=None):
+    """pool / tokens int32 [P, Npool] (each problem's samples; tokens may be None), truth int32 [P].  For every k in ``draws`` (any k up to
+    IID_MAX_DRAWS = 65535, also above Npool): the accuracy of the majority vote over k answers drawn WITH replacement from the pool -- the
+    plug-in estimate of maj@k, averaged over ``resamples`` draw sequences (Engine.iid_prefix, scv_iid_prefix_i32) -- and the tokens of the
+    draws, as records {'samples': k, 'accuracy', 'avg_tokens_used'} (avg_tokens_used is 0.0 without tokens).  The last record is
+    {'samples': inf, 'accuracy'}: the k -> infinity limit, which is the vote over the whole pool (Engine.aggregate_prefix at k = Npool).
+    With ``token_limits`` (each >= 2^11, the reference's grid: resampled_budgets) instead of ``draws`` (None), k = T // 2^11 whatever the
+    size of the pool, and every record but the last also carries 'token_limit'."""
+    pool = np.asarray(pool, dtype=np.int32)
+    if token_limits is not None:
+        if draws is not None:
+            raise ValueError("give draws or token_limits, not both")
+        budgets = resampled_budgets(token_limits)
+        draws = [n for _t, n in budgets]
+    draws = [int(k) for k in draws]
+    recs = []
+    if draws:
+        res = engine.iid_prefix(pool, truth, np.array(draws, dtype=np.int32), resamples, seed, tokens=tokens, M=0)
+        for b, k in enumerate(draws):
+            rec = {"samples": k, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b)) if tokens is not None else 0.0}
+            if token_limits is not None:
+                rec["token_limit"] = budgets[b][0]
+            recs.append(rec)
+    whole = engine.aggregate_prefix(pool, truth, np.array([pool.shape[1]], dtype=np.int32), want_cells=False)
+    recs.append({"samples": float("inf"), "accuracy": whole.accuracy(0)})
+    return recs
