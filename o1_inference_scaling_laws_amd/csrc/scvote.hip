@@ -1366,7 +1366,12 @@ int host_pipelined(scv_ctx* ctx, bool prefix, const int32_t* answers, const int3
     int64_t* d_tok = d_tie + (size_t)B * SCV_TIE_CLASSES;
     int64_t* d_ts = d_tok + B;
     hipStream_t s = ctx->stream, cs = hp->copy_stream;
-    SCV_HIP(hipMemsetAsync(sbase + o_cnt, 0, counters_bytes > 0 ? counters_bytes : 1, s));
+    // the kernels report into the block's own error word for this call, as in host_small and stage_call (restored on every path): what a DEVICE-mode
+    // call queued earlier left in the context's word stays there for scv_sync
+    const size_t o_err = o_cnt + align_up(counters_bytes, 256);
+    SCV_HIP(hipMemsetAsync(sbase + o_cnt, 0, o_err + sizeof(uint32_t) - o_cnt, s));
+    struct ErrSwap { scv_ctx* c; uint32_t* keep; bool dirty; ~ErrSwap() { c->d_err = keep; c->err_dirty = dirty; } } swap{ctx, ctx->d_err, ctx->err_dirty};
+    ctx->d_err = reinterpret_cast<uint32_t*>(sbase + o_err);
     if (n_valid && B > 0) SCV_HIP(hipMemcpyAsync(sbase + o_nv, n_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     // buffers the caller pinned are DMA'd in place; pageable ones go through the pinned bounce slots
     const bool pin_a = is_pinned_host(answers), pin_t = !tokens || is_pinned_host(tokens);
@@ -1435,9 +1440,9 @@ int host_pipelined(scv_ctx* ctx, bool prefix, const int32_t* answers, const int3
         if (token_sum_out) SCV_HIP(hipMemcpyAsync(token_sum_out, d_tok, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
         if (truth_count_sum_out) SCV_HIP(hipMemcpyAsync(truth_count_sum_out, d_ts, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     }
-    SCV_HIP(hipStreamSynchronize(s));
     uint32_t w = 0;
-    if (int rc = fetch_err(ctx, &w)) return rc;
+    SCV_HIP(hipMemcpyAsync(&w, ctx->d_err, sizeof w, hipMemcpyDeviceToHost, s));
+    SCV_HIP(hipStreamSynchronize(s));
     return check_err_word(ctx, w);
 }
 

@@ -49,8 +49,11 @@ def prefix_cell(votes, weights, truth: int, rule: int):
     return top, tw, len(modes), modes[0], hit, Fraction(1, len(modes)) if hit else Fraction(0)
 
 
-def weighted_prefix(pool, weights, truth, n_valid, rule, r_begin=0, r_end=None, seed=0, p_offset=0, tokens=None):
-    """Returns (tie[b] = {n_modes: hits}, score_sum[b] (Fraction), token_sum[b], cells[p][b] (pool order only, else None))."""
+def weighted_prefix(pool, weights, truth, n_valid, rule, r_begin=0, r_end=None, seed=0, p_offset=0, tokens=None, per_out=None,
+                    cell_tokens_out=None):
+    """Returns (tie[b] = {n_modes: hits}, score_sum[b] (Fraction), token_sum[b], cells[p][b] (pool order only, else None)).
+    ``per_out``: a caller's [R][B][M] lists of zeros, filled with the hits of every ordering by n_modes (< M).  ``cell_tokens_out``: a
+    caller's [P][B] lists, filled with the tokens of every prefix (pool order, with tokens)."""
     P, N = len(pool), len(pool[0])
     B = len(n_valid)
     shuffled = r_end is not None
@@ -60,7 +63,7 @@ def weighted_prefix(pool, weights, truth, n_valid, rule, r_begin=0, r_end=None, 
     toks = [0] * B
     cells = None if shuffled else [[None] * B for _ in range(P)]
     for p in range(P):
-        for r in rs:
+        for ri, r in enumerate(rs):
             pi = permutation(seed, p_offset + p, r, N) if shuffled else list(range(N))
             for b in range(B):
                 k = min(max(int(n_valid[b]), 0), N)
@@ -68,9 +71,13 @@ def weighted_prefix(pool, weights, truth, n_valid, rule, r_begin=0, r_end=None, 
                 top, tw, nm, mm, hit, sc = prefix_cell([int(pool[p][i]) for i in idx], [int(weights[p][i]) for i in idx], int(truth[p]), rule)
                 if hit:
                     tie[b][nm] = tie[b].get(nm, 0) + 1
+                    if per_out is not None and nm < len(per_out[ri][b]):
+                        per_out[ri][b][nm] += 1
                 score[b] += sc
                 if tokens is not None:
                     toks[b] += sum(int(tokens[p][i]) for i in idx)
+                    if cell_tokens_out is not None:
+                        cell_tokens_out[p][b] = sum(int(tokens[p][i]) for i in idx)
                 if cells is not None:
                     cells[p][b] = (top, tw, nm, mm, int(hit))
     return tie, score, toks, cells
