@@ -1919,30 +1919,41 @@ int scv_bootstrap(scv_ctx* ctx, const scv_cell* cells, int64_t P, int32_t B, int
         // global-gather kernel.  "boot_path" = 3 forces the latter (parity tests).
         const size_t lds_fast = (((size_t)B * M + 3) & ~(size_t)3) * sizeof(uint32_t) + (((size_t)P * B + 7) & ~(size_t)7) * sizeof(uint16_t);
         const bool fast = ctx->boot_path != 3 && lds_fast <= (size_t)144 * 1024;
-        auto launch_boot = [&](const scv_cell* d_cells, unsigned long long* d_out) -> int {
+        auto launch_boot = [&](const scv_cell* d_cells, unsigned long long* d_out, uint32_t* d_err) -> int {
             if (fast) {
                 int64_t grid = (int64_t)ctx->num_cus;                          // one 1024-thread workgroup per CU, R / grid resamples each
                 if (grid > R) grid = R;
                 SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scv::scv_bootstrap_lds_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast));
-                hipLaunchKernelGGL(scv::scv_bootstrap_lds_k, dim3((unsigned)grid), dim3(1024), lds_fast, s, d_cells, P, B, r_begin, r_end, seed, M, d_out, ctx->d_err);
+                hipLaunchKernelGGL(scv::scv_bootstrap_lds_k, dim3((unsigned)grid), dim3(1024), lds_fast, s, d_cells, P, B, r_begin, r_end, seed, M, d_out, d_err);
             } else {
-                hipLaunchKernelGGL(scv::scv_bootstrap_k, dim3((unsigned)R), dim3(256), lds, s, d_cells, P, B, r_begin, seed, M, d_out, ctx->d_err);
+                hipLaunchKernelGGL(scv::scv_bootstrap_k, dim3((unsigned)R), dim3(256), lds, s, d_cells, P, B, r_begin, seed, M, d_out, d_err);
             }
             SCV_HIP(hipGetLastError());
-            ctx->err_dirty = true;
             return SCV_OK;
         };
-        if (mem_kind == SCV_MEM_DEVICE) return launch_boot(cells, reinterpret_cast<unsigned long long*>(counts_out));
+        if (mem_kind == SCV_MEM_DEVICE) {
+            if (int rc = launch_boot(cells, reinterpret_cast<unsigned long long*>(counts_out), ctx->d_err)) return rc;
+            ctx->err_dirty = true;
+            return SCV_OK;
+        }
         const size_t cells_bytes = (size_t)P * B * sizeof(scv_cell);
         const size_t o_out = align_up(cells_bytes, 256);
-        if (int rc = ensure_stage(ctx, o_out + out_bytes)) return rc;
+        // the kernel reports into the block's own error word for this call, as in host_small, stage_call and host_pipelined: what a
+        // DEVICE-mode call queued earlier left in the context's word stays there, with err_dirty, for scv_sync
+        const size_t o_err = align_up(o_out + out_bytes, 256);
+        if (int rc = ensure_stage(ctx, o_err + 256)) return rc;
         char* base = static_cast<char*>(ctx->d_stage);
+        uint32_t* d_err = reinterpret_cast<uint32_t*>(base + o_err);
+        SCV_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s));
         SCV_HIP(hipMemcpyAsync(base, cells, cells_bytes, hipMemcpyHostToDevice, s));
-        if (int rc = launch_boot(reinterpret_cast<const scv_cell*>(base), reinterpret_cast<unsigned long long*>(base + o_out))) return rc;
-        SCV_HIP(hipMemcpyAsync(counts_out, base + o_out, out_bytes, hipMemcpyDeviceToHost, s));
-        SCV_HIP(hipStreamSynchronize(s));
+        if (int rc = launch_boot(reinterpret_cast<const scv_cell*>(base), reinterpret_cast<unsigned long long*>(base + o_out), d_err)) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
         uint32_t w = 0;
-        if (int rc = fetch_err(ctx, &w)) return rc;
+        SCV_HIP(hipMemcpyAsync(counts_out, base + o_out, out_bytes, hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipMemcpyAsync(&w, d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        SCV_HIP(hipStreamSynchronize(s));
         return check_err_word(ctx, w);
     });
 }

@@ -633,7 +633,8 @@ __device__ __forceinline__ void bootstrap_in_launch(const AggArgs& a, uint32_t* 
         tab[i] = ((hi >> 32) & 0xffu) ? (uint16_t)(hi & 0xffffu) : (uint16_t)0;
     }
     const int32_t M = a.boot_M;
-    for (int32_t r = a.boot_r0 + (int32_t)blockIdx.x; r < a.boot_r1; r += (int32_t)gridDim.x) {
+    // r in 64 bits: boot_r1 may be 2^31 - 1, and the last r + gridDim.x of a workgroup passes it
+    for (int64_t r = (int64_t)a.boot_r0 + blockIdx.x; r < a.boot_r1; r += gridDim.x) {
         for (int64_t i = tid; i < BM; i += T) cnt[i] = 0;
         __syncthreads();
         uint64_t arg = a.boot_seed + kGolden * ((uint64_t)r * (uint64_t)a.P + (uint64_t)tid + 1);
@@ -655,7 +656,7 @@ __device__ __forceinline__ void bootstrap_in_launch(const AggArgs& a, uint32_t* 
             }
         }
         __syncthreads();
-        unsigned long long* o = a.boot_out + (int64_t)(r - a.boot_r0) * BM;
+        unsigned long long* o = a.boot_out + (r - a.boot_r0) * BM;
         for (int64_t i = tid; i < BM; i += T) o[i] = cnt[i];
         __syncthreads();
     }
@@ -2995,7 +2996,8 @@ __global__ __launch_bounds__(1024) void scv_bootstrap_lds_k(const scv_cell* cell
     }
     bool overflow = false;
     const int64_t BM = (int64_t)B * M;
-    for (int32_t r = r_begin + (int32_t)blockIdx.x; r < r_end; r += (int32_t)gridDim.x) {
+    // r in 64 bits: r_end may be 2^31 - 1, and the last r + gridDim.x of a workgroup passes it
+    for (int64_t r = (int64_t)r_begin + blockIdx.x; r < r_end; r += gridDim.x) {
         for (int64_t i = tid; i < BM; i += T) cnt[i] = 0;
         __syncthreads();                                                   // table staged (first pass) / counters zero
         // uniform trip count per wave (the ballot needs the whole wave): draws past P contribute nothing.
@@ -3022,7 +3024,7 @@ __global__ __launch_bounds__(1024) void scv_bootstrap_lds_k(const scv_cell* cell
             }
         }
         __syncthreads();
-        unsigned long long* o = out + (int64_t)(r - r_begin) * BM;
+        unsigned long long* o = out + (r - r_begin) * BM;
         for (int64_t i = tid; i < BM; i += T) o[i] = cnt[i];
         __syncthreads();                                                   // before the next resample re-zeroes cnt
     }
