@@ -826,14 +826,23 @@ class MultiDeviceEngine:
     def __exit__(self, *exc):
         self.close()
 
+    def _bind_torch_streams(self):
+        """The collectives take torch tensors, so like every DEVICE-mode method of ``Engine`` they run on torch's current stream of each
+        engine's device, behind the torch ops that produced their inputs (scv_allreduce_counters itself uses whatever stream each
+        context has: a fresh context's private non-blocking stream waits for nothing torch has queued)."""
+        for e in self.engines:
+            e.use_torch_stream()
+
     def all_reduce_counters(self, counters):
         """``counters[g]``: int64 CUDA tensor on engine g's device (equal lengths).  In-place SUM over the engines through the
-        library's communicator (scv_allreduce_counters), ordered behind the engines' queued work; asynchronous."""
+        library's communicator (scv_allreduce_counters) on torch's current stream of each engine's device, ordered behind the
+        engines' queued work; asynchronous."""
         n = int(counters[0].numel())
         for e, c in zip(self.engines, counters):
             if int(c.numel()) != n or not c.is_contiguous():
                 raise ValueError("counters must be contiguous int64 tensors of one length")
             e._check_device(c, "counters")
+        self._bind_torch_streams()
         ptrs = (C.c_void_p * len(counters))(*[c.data_ptr() for c in counters])
         check(self._L.scv_allreduce_counters(self._comm, ptrs, n))
         return counters
@@ -856,6 +865,7 @@ class MultiDeviceEngine:
             if tuple(t.shape) != (P, B, 16) or not t.is_contiguous():
                 raise ValueError("tables must be contiguous uint8 [P, B, 16] tensors of one shape")
             e._check_device(t, "tables")
+        self._bind_torch_streams()
         ptrs = (C.c_void_p * len(tables))(*[t.data_ptr() for t in tables])
         check(self._L.scv_allgather_cells(self._comm, ptrs, (C.c_int64 * len(rows))(*[int(r) for r in rows]), B))
         return tables
@@ -868,6 +878,7 @@ class MultiDeviceEngine:
             if int(b.numel()) < tot or not b.is_contiguous():
                 raise ValueError("buffers must be contiguous int64 tensors of at least sum(counts) words")
             e._check_device(b, "buffers")
+        self._bind_torch_streams()
         ptrs = (C.c_void_p * len(buffers))(*[b.data_ptr() for b in buffers])
         check(self._L.scv_allgather_i64(self._comm, ptrs, (C.c_int64 * len(counts))(*[int(c) for c in counts])))
         return buffers
