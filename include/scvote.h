@@ -50,7 +50,11 @@ extern "C" {
                                       -- max_count 0 -- has min_mode field 1023 and means -1).  The reference's most common call is N = 1
                                       (o1.py:302) and N = 1, 2, 4, 8 (o1.py:276): a 16-byte scv_cell per 4-byte vote is 80 % of such a launch's traffic.
                                       Everything else (counters, cell_tokens) is unchanged; a call the flag does not cover (prefix budgets, HOST memory,
-                                      N > 127, a forced streaming path, vote + bootstrap) with cells_out != NULL is SCV_ERR_ARG.  Decoder:
+                                      N > 127, a forced streaming path, vote + bootstrap) with cells_out != NULL is SCV_ERR_ARG -- and so is one
+                                      whose options send the cells to a kernel that writes 16-byte records only: the streaming kernel ("reg_n_max"
+                                      below N, with the sort off or N > 64) or a dense register shape ("reg_shape" 1041 .. 1048); nothing is queued.
+                                      The 4-byte record is written by the one-lane-per-cell kernels, the sorted cells and the sparse register
+                                      shapes (csrc/scvote_plan.h packed_ok).  Without a cell table every kernel serves such a context.  Decoder:
                                       o1_inference_scaling_laws_amd/engine.py unpack_cells */
 
 /* synthetic distributions */
@@ -165,13 +169,20 @@ int scv_set_option(scv_ctx* ctx, const char* key, int64_t value);
  *   o1.py:204-213 (tie-aware score) and the integer part of o1.py:229-245 (per-budget sums).
  *
  * Outputs (any may be NULL):
- *   cells_out            scv_cell [P, B]
- *   cell_tokens_out      int64    [P, B]   sum of tokens over the valid prefix (o1.py:195)
- *   tie_class_hits_out   int64    [B, 1025] #problems with hit and n_modes == m  (o1.py:238-239)
- *   token_sum_out        int64    [B]       sum over problems of cell_tokens     (o1.py:240,245)
- *   truth_count_sum_out  int64    [B]       sum over problems of truth_count
+ *   cells_out            scv_cell [P, B]                                                    DEVICE memory: 16-byte aligned
+ *   cell_tokens_out      int64    [P, B]   sum of tokens over the valid prefix (o1.py:195); DEVICE memory: 16-byte aligned;
+ *                                           written only by a call with tokens, untouched without
+ *   tie_class_hits_out   int64    [B, 1025] #problems with hit and n_modes == m  (o1.py:238-239)  DEVICE memory: 8-byte aligned
+ *   token_sum_out        int64    [B]       sum over problems of cell_tokens     (o1.py:240,245)  DEVICE memory: 8-byte aligned
+ *   truth_count_sum_out  int64    [B]       sum over problems of truth_count                      DEVICE memory: 8-byte aligned
  * In DEVICE mode the three per-budget outputs are ACCUMULATED INTO (+=), so a caller streaming
  * problem-chunks (or ranks before an all-reduce) zeroes them once; in HOST mode they are overwritten.
+ * In DEVICE mode the kernels store into the caller's arrays directly, and the alignment above is the widest store each output receives:
+ * 16 bytes for the cell tables (whole records; with SCV_FLAG_PACKED_CELLS four / two consecutive 4-byte records per lane at N = 1 / 2 -- a
+ * uint32 [P, B] table needs 16 bytes too; two consecutive cell_tokens per lane at N = 1 / 2 and in scv_sort_prefix), 8 bytes for the
+ * counters (64-bit atomics and stores).  A pointer below its alignment is SCV_ERR_ARG with nothing queued -- also through
+ * scv_aggregate_prefix_i32 and scv_aggregate_bootstrap_i32.  (A row of a larger scv_cell table is always aligned when the table is; a row
+ * of a cell_tokens table is when P_row * B is even.)  HOST memory has no such requirement.
  */
 int scv_aggregate_i32(scv_ctx* ctx,
                       const int32_t* answers, const int32_t* tokens,

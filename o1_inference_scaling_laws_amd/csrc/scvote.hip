@@ -299,7 +299,7 @@ scv::AggArgs agg_args(const scv_ctx* ctx, const AggCall& c) {
     scv::AggArgs a;
     a.answers = c.answers; a.tokens = c.tokens; a.n_valid = c.n_valid; a.truth = c.truth;
     a.ncells = c.ncells(); a.N = c.N; a.B = c.B; a.P = c.P;
-    a.cells = c.cells; a.cell_tokens = c.cell_tokens;
+    a.cells = c.cells; a.cell_tokens = c.tok() ? c.cell_tokens : nullptr;      // cell_tokens_out is written only by a call with tokens, in both memory modes
     a.tie_hits = reinterpret_cast<unsigned long long*>(c.tie);
     a.token_sum = reinterpret_cast<unsigned long long*>(c.tok_sum); a.truth_sum = reinterpret_cast<unsigned long long*>(c.truth_sum);
     a.err_flag = ctx->d_err;
@@ -373,11 +373,18 @@ int resident_per_cu(KernelFn fn, int threads, size_t lds, int* per_cu) {
 // The reference's own range (N = 1 ... 128, o1.py:267,276).  Rows that are not all 16-byte aligned (N % 4 != 0, unaligned
 // bases) take the linear-image form (dword reads).
 // *fits = false, nothing queued: the launch does not fit the LDS (hundreds of budgets; plan::sort_fallback_kind says who takes the call)
+// waves per workgroup of the sorted-cells launch of this call; 0: it does not fit the LDS
+int sorted_cells_waves(const scv_ctx* ctx, const AggCall& c) {
+    const int nv = plan::sort_nv(c.N);
+    const RegKernel rk = pick_sort_kernel(nv, c.tok(), !c.rows_aligned());
+    return plan::sort_waves(rk.waves, plan::sort_region_words(c.N, c.tok(), !c.rows_aligned()), plan::sort_tail_words(c.n_valid != nullptr, c.B, nv), ctx->lds_max);
+}
+
 int launch_sorted_cells(scv_ctx* ctx, const AggCall& c, scv::AggArgs& a, TimedSpan& span, bool* fits) {
     const int nv = plan::sort_nv(c.N);
     const RegKernel rk = pick_sort_kernel(nv, c.tok(), !c.rows_aligned());
     const int64_t region_words = plan::sort_region_words(c.N, c.tok(), !c.rows_aligned()), tail_words = plan::sort_tail_words(c.n_valid != nullptr, c.B, nv);
-    const int W = plan::sort_waves(rk.waves, region_words, tail_words, ctx->lds_max);
+    const int W = sorted_cells_waves(ctx, c);
     if (!(*fits = W != 0)) return SCV_OK;
     a.wave_lds_words = (int32_t)region_words;
     const size_t lds = (size_t)(W * region_words + tail_words) * sizeof(uint32_t);
@@ -398,12 +405,18 @@ int launch_sorted_cells(scv_ctx* ctx, const AggCall& c, scv::AggArgs& a, TimedSp
 }
 
 // ---- register-resident cells: workgroups of independent waves, 8 KiB of LDS each
-int launch_reg_cells(scv_ctx* ctx, const AggCall& c, scv::AggArgs& a, bool lds_counters, TimedSpan& span) {
+// the register shape launch_reg_cells gives this call (plan::reg_shape; option "reg_shape" forces one)
+plan::RegShape call_reg_shape(const scv_ctx* ctx, const AggCall& c) {
     const bool tok = c.tok(), vec = c.rows_aligned();
     const int64_t Nreg = vec ? c.N : c.N + 3;      // unaligned rows are read as their aligned supersets
     const int fv = ctx->reg_shape % 100;
     const bool have_g8 = ctx->reg_shape / 100 == 8 && (fv == 3 || fv == 4) && scv::pick_reg_g8(fv, tok, vec).fn != nullptr;
-    const plan::RegShape shape = plan::reg_shape(Nreg, ctx->reg_shape, have_g8);
+    return plan::reg_shape(Nreg, ctx->reg_shape, have_g8);
+}
+
+int launch_reg_cells(scv_ctx* ctx, const AggCall& c, scv::AggArgs& a, bool lds_counters, TimedSpan& span) {
+    const bool tok = c.tok(), vec = c.rows_aligned();
+    const plan::RegShape shape = call_reg_shape(ctx, c);
     const int64_t cpw = shape.h ? 1 : 64 / shape.g;
     const int64_t nbatches = (a.ncells + cpw - 1) / cpw;
     a.wave_lds_words = (int32_t)(scv::kRegWaveWords16 + plan::nv_cache_words(c.n_valid != nullptr, c.B));
@@ -575,8 +588,20 @@ int launch_cells(scv_ctx* ctx, const plan::Options& o, const AggCall& c, bool po
     if (c.ncells() == 0) return SCV_OK;
     scv::AggArgs a = agg_args(ctx, c);
     a.pool_rows = pool_rows ? 1 : 0; a.prefetch = 1;
-    a.packed_cells = ((ctx->flags & SCV_FLAG_PACKED_CELLS) && c.cells && !pool_rows) ? 1 : 0;   // (aggregate_common has checked the shape: N <= 127, cell kernels only)
     plan::Kind kind = plan::cell_kind(o, c.N, c.B, c.rows_aligned(), c.tok(), pool_rows);
+    // 4-byte records (aggregate_common has checked the call form and N <= 127): only the kernels of plan::packed_ok write them.  Options can send
+    // such cells elsewhere ("reg_n_max" below N: the streaming kernel; "reg_shape" 1041 .. 1048: the dense parts), where a 16-byte record per cell
+    // would overrun the caller's 4-byte-per-cell table: refused here, with the kernel that would RUN known and nothing queued yet.
+    const bool packed = (ctx->flags & SCV_FLAG_PACKED_CELLS) && c.cells && !pool_rows;
+    if (packed) {
+        plan::Kind runs = kind;
+        if (runs == plan::SORT && sorted_cells_waves(ctx, c) == 0) runs = plan::sort_fallback_kind(o, c.N, c.B);
+        if (!plan::packed_ok(runs, call_reg_shape(ctx, c)))
+            return fail(SCV_ERR_ARG, "SCV_FLAG_PACKED_CELLS: options reg_n_max=%d sort_n_max=%d reg_shape=%d send cells of N=%lld votes to a kernel that writes "
+                                     "16-byte records (the streaming kernel or a dense register shape); call without a cell table or change the options",
+                        ctx->reg_n_max, ctx->sort_n_max, ctx->reg_shape, (long long)c.N);
+    }
+    a.packed_cells = packed ? 1 : 0;
     if (kind == plan::STREAM) return launch_stream(ctx, o, c, a);
     // the cell kernels count in their own LDS tables (scv_reduce_cells only when forced) and accumulate: overwrite = memset nodes in front
     const bool want_counters = c.want_counters();
@@ -1254,6 +1279,17 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
         if (prefix || mem_kind != SCV_MEM_DEVICE || N > 127 || (ctx->path >= 1 && ctx->path <= 3) || ctx->fused_counters_max == 0 || ctx->boot_req)
             return fail(SCV_ERR_ARG, "SCV_FLAG_PACKED_CELLS: cells_out is uint32 [P, B] only for scv_aggregate_i32 on DEVICE memory with N <= 127 "
                                      "(auto dispatch; no prefix budgets, no bootstrap in the call); got prefix=%d mem_kind=%d N=%lld", (int)prefix, mem_kind, (long long)N);
+    }
+    if (mem_kind == SCV_MEM_DEVICE) {
+        // The kernels store into the caller's arrays directly, with the widest store each output receives: 16 bytes for the two cell tables (whole
+        // scv_cell records; four / two consecutive 4-byte records per lane of scv_one_vote / scv_two_votes; two consecutive cell_tokens per lane of
+        // those kernels and of scv_sort_prefix), 8 bytes for the counters (64-bit atomics, the overwrite epilogue's 64-bit stores).  Nothing is queued
+        // for a pointer below that.
+        if ((((uintptr_t)cells_out | (uintptr_t)cell_tokens_out) & 15u) != 0)
+            return fail(SCV_ERR_ARG, "DEVICE memory: cells_out and cell_tokens_out must be 16-byte aligned (got %p, %p)", (void*)cells_out, (void*)cell_tokens_out);
+        if ((((uintptr_t)tie_class_hits_out | (uintptr_t)token_sum_out | (uintptr_t)truth_count_sum_out) & 7u) != 0)
+            return fail(SCV_ERR_ARG, "DEVICE memory: tie_class_hits_out, token_sum_out and truth_count_sum_out must be 8-byte aligned (got %p, %p, %p)",
+                        (void*)tie_class_hits_out, (void*)token_sum_out, (void*)truth_count_sum_out);
     }
     SCV_ENTER(ctx);
     auto launch = prefix ? launch_prefix : launch_aggregate;

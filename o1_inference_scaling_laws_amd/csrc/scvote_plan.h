@@ -135,6 +135,12 @@ inline RegShape reg_shape(int64_t Nreg, int forced, bool have_g8) {
     }
     return RegShape{g, v, h};
 }
+// SCV_FLAG_PACKED_CELLS: the kernels that write the 4-byte record (they call pack_cell, scvote_kernels.hip.h / scvote_sort.hip.h): one lane per cell
+// (scv_lane_cells, scv_few_votes, scv_one_vote, scv_two_votes), sorted cells (scv_sort_cells) and the SPARSE register-resident shapes (scv_reg_cells).
+// The dense register-resident parts (scv_reg_dense) and the streaming kernel (scv_hist_argmax, and scv_reduce_cells reading its table) know 16-byte
+// records only: a packed context with a cell table must not reach them (launch_cells refuses the call).  kind: the kernel that RUNS (behind
+// sort_fallback_kind when the sorted launch does not fit); s: the register shape of the call (read for REG only).
+inline bool packed_ok(Kind kind, const RegShape& s) { return kind == LANE || kind == SORT || (kind == REG && s.h == 0); }
 // The grid is persistent, so it must not exceed what is resident at once (CUs x the runtime's occupancy answer, or the forced grid).  A wave strides over
 // the batches by grid * WPG: keep the stride coprime with B so that every wave visits every budget (ragged n_valid would otherwise give some waves only the long budgets)
 inline int64_t reg_grid(int64_t resident, int64_t nbatches, int WPG, int32_t B) {

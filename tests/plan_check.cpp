@@ -48,6 +48,7 @@ int main() {
         else if (q == "lanelds") { need(2); printf("%zu\n", lane_kernel_lds((int32_t)a[0], (int)a[1])); }
         else if (q == "kind") { need(5); printf("%s\n", kinds[cell_kind(o, a[0], (int32_t)a[1], a[2] != 0, a[3] != 0, a[4] != 0)]); }     // N B rows_aligned tok pool_rows
         else if (q == "sortfb") { need(2); printf("%s\n", kinds[sort_fallback_kind(o, a[0], (int32_t)a[1])]); }                             // N B
+        else if (q == "packed") { need(4); if (a[0] < 0 || a[0] > 3) { fprintf(stderr, "bad kind: %s\n", line.c_str()); return 2; } printf("%d\n", (int)packed_ok((Kind)a[0], RegShape{(int)a[1], (int)a[2], (int)a[3]})); }   // kind (0 LANE 1 SORT 2 REG 3 STREAM) g v h
         else if (q == "shape") { need(3); const RegShape s = reg_shape(a[0], (int)a[1], a[2] != 0); printf("%d %d %d\n", s.g, s.v, s.h); }      // Nreg forced have_g8
         else if (q == "reggrid") { need(4); printf("%lld\n", (long long)reg_grid(a[0], a[1], (int)a[2], (int32_t)a[3])); }                   // resident nbatches WPG B
         else if (q == "band") { need(2); const StreamBand b = stream_band(o, a[0], a[1]); printf("%d %d %d %d %zu\n", b.copies, b.threads, b.wg_per_cu, b.unroll, b.lds); }   // N ncells

@@ -87,6 +87,47 @@ case("sortfb 8 1181", "LANE")
 case("sortfb 8 1182", "REG")
 case("sortfb 40 1", "REG")
 
+# ---- 4-byte records (SCV_FLAG_PACKED_CELLS, N <= 127): packed kind g v h -> served; kind 0 LANE 1 SORT 2 REG 3 STREAM.  Only the kernels that call
+# pack_cell write them: one lane per cell, sorted cells, the sparse register shapes.  The rows below walk the options that move such cells to
+# another kernel, on both sides: kind says who runs, shape which register shape, packed whether launch_cells serves the call.
+case("packed 0 0 0 0", 1)
+case("packed 1 0 0 0", 1)
+case("packed 2 16 1 0", 1)
+case("packed 2 8 3 0", 1)
+case("packed 2 8 4 0", 1)
+case("packed 2 16 2 0", 1)
+case("packed 2 0 4 1", 0)                 # the dense parts write 16-byte records
+case("packed 2 0 4 8", 0)
+case("packed 3 0 0 0", 0)                 # so does the streaming kernel (and scv_reduce_cells reads them)
+case("packed 3 16 1 0", 0)
+# reg_n_max at N and at N - 1, N = 100 (aligned rows) and N = 101 (unaligned)
+case("kind 100 1 1 0 0", "REG", reg_n_max=100)
+case("kind 100 1 1 0 0", "STREAM", reg_n_max=99)
+case("kind 101 1 0 0 0", "REG", reg_n_max=101)
+case("kind 101 1 0 0 0", "STREAM", reg_n_max=100)
+case("kind 65 1 0 0 0", "STREAM", reg_n_max=64)
+case("kind 127 1 0 0 0", "STREAM", reg_n_max=0)
+# N = 40: the sort on / off, reg_n_max at N and at N - 1 (tiny_n_max = 32 is below)
+case("kind 40 1 1 0 0", "SORT", reg_n_max=39)                   # the sort is asked first: reg_n_max does not matter
+case("kind 40 1 1 0 0", "REG", sort_n_max=0, reg_n_max=40)
+case("kind 40 1 1 0 0", "STREAM", sort_n_max=0, reg_n_max=39)
+case("kind 40 1 1 0 0", "STREAM", sort_n_max=32, reg_n_max=39)   # (switched off for this N by its upper bound)
+case("kind 32 1 1 0 0", "LANE", sort_n_max=0, reg_n_max=0)      # up to tiny_n_max one lane per cell whatever reg_n_max
+case("kind 33 1 0 0 0", "STREAM", sort_n_max=0, reg_n_max=32)
+case("kind 20 1 1 1 0", "REG", sort_n_max=0, reg_n_max=0)       # tokens from 17 votes: LANE hands over to REG after reg_n_max was asked
+# the sorted launch that does not fit falls back to LANE or REG, never to the streaming kernel
+case("sortfb 40 1", "REG", reg_n_max=0)
+case("sortfb 100 1", "REG", reg_n_max=0)
+# forced dense codes are honoured at N = 100 (1024 .. 8192 slots), forced sparse codes give sparse shapes, codes too small fall back to sparse
+for code, h in ((1041, 1), (1042, 2), (1044, 4), (1048, 8)):
+    case(f"shape 100 {code} 0", (0, 4, h))
+    case(f"shape 103 {code} 0", (0, 4, h))                       # N = 100 in unaligned rows
+for code, want in ((1601, (8, 4, 0)), (1602, (16, 2, 0)), (1604, (16, 4, 0)), (3204, (32, 4, 0)), (6404, (64, 4, 0)), (803, (8, 4, 0)), (804, (8, 4, 0))):
+    case(f"shape 100 {code} 1", want)                            # (1601 / 803: 64 / 96 slots are too few for 100 -> the auto shape (8, 4))
+case("shape 100 0 0", (8, 4, 0))
+case("shape 64 1041 0", (0, 4, 1))
+case("shape 1 1048 0", (0, 4, 8))
+
 # ---- register shape: shape Nreg forced have_g8 -> g v h ---------------------------------------------------------------------------------
 for nreg, want in ((64, (16, 1, 0)), (65, (8, 3, 0)), (96, (8, 3, 0)), (97, (8, 4, 0)), (128, (8, 4, 0)), (129, (16, 4, 0)), (256, (16, 4, 0)),
                    (257, (32, 4, 0)), (512, (32, 4, 0)), (513, (64, 4, 0)), (896, (64, 4, 0)), (897, (0, 4, 1)), (1024, (0, 4, 1)),
@@ -339,7 +380,7 @@ def test_the_boundaries_of_the_issue_are_covered():
     by = {}
     for _, query, want in CASES:
         by.setdefault(query.split()[0], set()).add(want)
-    for q in ("nv", "kind", "sortfb", "shape", "reggrid", "band", "split", "grid", "disp", "reduce", "owfew", "chunks", "tcl", "tclds", "nvc", "lanegrid", "bgrid",
+    for q in ("nv", "kind", "sortfb", "packed", "shape", "reggrid", "band", "split", "grid", "disp", "reduce", "owfew", "chunks", "tcl", "tclds", "nvc", "lanegrid", "bgrid",
               "few", "sortw", "spw", "plane", "served", "spe", "form", "rows", "ppl"):
         assert len(by.get(q, ())) >= 2, q
     assert by["kind"] == {"LANE", "SORT", "REG", "STREAM"} and by["form"] == {"POOL", "CELLS", "LANE", "HIST"}
