@@ -57,6 +57,24 @@ extern "C" {
                                       shapes (csrc/scvote_plan.h packed_ok).  Without a cell table every kernel serves such a context.  Decoder:
                                       o1_inference_scaling_laws_amd/engine.py unpack_cells */
 
+#define SCV_FLAG_OPEN_DOMAIN 0x8u /* OPT-IN: the six pool-ordering entries (scv_resample_prefix_i32, scv_expected_majority_i32, scv_token_budget_prefix_i32,
+                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32) take ANY int32 as an answer value: negative
+                                      numbers, large integers, 32-bit hashes of normalised answer strings.  Two votes are the same value only when
+                                      the integers are equal.  A vote's code is the rank of its value among the distinct values of the whole row
+                                      pool[p, 0:N] in ascending SIGNED order -- what the byte codes of these entries already are for rows inside
+                                      0..1023 -- and everything downstream walks codes, so nothing else changes: the permutation for (seed, pg, r),
+                                      the draw streams, the token sums; slices of r and shards of p still add up bit for bit; HOST mode and hipGraph
+                                      capture work as without the flag.  The truth hits exactly when it equals a modal value, whatever its
+                                      magnitude.  Under the flag these six entries never set error bit 0 (no SCV_ERR_DOMAIN), and
+                                      SCV_FLAG_CLAMP_TO_INVALID_BIN has no effect on them; every other error bit (1, 4, 5, 6, 7, 8) keeps its meaning.
+                                      cells_out[..].min_mode (SCV_ORDER_POOL calls of the token-budget, weighted and adaptive entries) is then the
+                                      CODE of the smallest modal value, 0 .. distinct - 1, or -1 for the empty cell -- not the value, which an
+                                      int16 cannot hold; o1_inference_scaling_laws_amd/engine.py decode_min_mode turns it back into the value.
+                                      With the flag off every entry behaves as before.  The dense entries (scv_aggregate_i32, scv_aggregate_prefix_i32,
+                                      scv_aggregate_bootstrap_i32, scv_bootstrap, scv_synth_fill_i32) ignore the flag in both states: they keep
+                                      the 1024 bins, and an out-of-domain vote is SCV_ERR_DOMAIN there as always.  Cost: the row encoder ranks by
+                                      counting in registers (csrc/scvote_resample.hip.h resample_encode_row_open), N broadcast steps per row. */
+
 /* synthetic distributions */
 #define SCV_DIST_UNIFORM 0        /* D0: uniform over 0..999                                    */
 #define SCV_DIST_PEAKED 1         /* D1: truth w.p. q_p in {.1...7}, 4 distractors at .05, rest uniform */
@@ -283,6 +301,7 @@ int scv_synth_fill_i32(scv_ctx* ctx, int32_t* answers, int32_t* tokens, int32_t*
  * k-subset, and the subsets of one resample are nested across budgets, as in the reference.  Cells follow the conventions of
  * scv_aggregate_prefix_i32: an empty subset has no hit; a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST
  * mode, at scv_sync in DEVICE mode) or counts in bin 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own: no domain error, no clamp, and a truth of any magnitude hits when it is a mode.
  * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
  *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m: accuracy_from_tie_classes(tie[b], P * R)
  *                        (o1_inference_scaling_laws_amd/scoring.py) is the expected maj@k_b, exact_accuracy_... its exact rational
@@ -321,6 +340,7 @@ int scv_resample_prefix_i32(scv_ctx* ctx,
  * Votes and truths follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at
  * scv_sync in DEVICE mode) or counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.  A negative token
  * count sets error bit 4: SCV_ERR_ARG at the call in HOST mode, at scv_sync in DEVICE mode.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own (no domain error, no clamp) and cells_out[..].min_mode is the CODE of the smallest modal value.
  * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
  *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
  *   token_sum_out        int64 [B]        (NULL ok) tokens actually spent
@@ -367,6 +387,7 @@ int scv_token_budget_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t
  * is below 2^32: all sums are exact.  A weight outside 0 .. SCV_WEIGHT_MAX sets error bit 5: SCV_ERR_ARG at the call in HOST mode, at
  * scv_sync in DEVICE mode.  Votes and truths follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN) or
  * counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own (no domain error, no clamp) and cells_out[..].min_mode is the CODE of the smallest modal value.
  * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
  *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
  *   token_sum_out        int64 [B]        (NULL ok; requires tokens) tokens of the samples in the prefixes
@@ -419,6 +440,7 @@ int scv_weighted_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* we
  * of m; o1_inference_scaling_laws_amd/adaptive.py builds these and the Beta criterion of Adaptive-Consistency.  Votes and truths follow
  * scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at scv_sync in DEVICE mode) or
  * counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own (no domain error, no clamp) and cells_out[..].min_mode is the CODE of the smallest modal value.
  * Outputs, summed over the P x (r_end - r_begin) cells of a rule:
  *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
  *   token_sum_out        int64 [B]        (NULL ok; requires tokens) tokens of the samples drawn
@@ -461,6 +483,7 @@ int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
  *            (no hit).  The budgets of one resample are nested prefixes of one draw sequence.
  * Votes, truths and the clamp flag follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in
  * HOST mode, at scv_sync in DEVICE mode) or counts in bin 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own: no domain error, no clamp, and a truth of any magnitude hits when it is a mode.
  * Outputs and their accumulation rules are those of scv_resample_prefix_i32, summed over the P x (r_end - r_begin) cells of a budget:
  *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational);
  *                        n_modes <= min(distinct values, k) <= N, so the table keeps its shape for k > N
@@ -498,6 +521,7 @@ int scv_iid_prefix_i32(scv_ctx* ctx,
  * (j truth votes in the subset; every other value at most j votes, u of them tied at exactly j).  Cells follow scv_resample_prefix_i32:
  * a vote outside 0..1023 counts as value 1023 and sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at scv_sync in DEVICE mode;
  * no error under SCV_FLAG_CLAMP_TO_INVALID_BIN); a truth outside the bins never hits; k = 0 scores 0.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own: no domain error, no clamp, and a truth of any magnitude counts as c_t when it is in the row.
  *   expected_score_out  float64 [P, B] (required)  E_k_b;  mean over p is the expected maj@k_b (curves.exact_majority_records)
  *   hit_prob_out        float64 [P, B] (NULL ok)   H_k_b
  * Computed in float64 with no subtraction anywhere (sum_u A / (1+u) = integral_0^1 A(s,y) dy by an exact Gauss-Legendre rule;

@@ -11,6 +11,7 @@ _lib = None
 # include/scvote.h constants
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_TIMING, FLAG_CLAMP, FLAG_PACKED_CELLS = 0x1, 0x2, 0x4
+FLAG_OPEN_DOMAIN = 0x8                        # SCV_FLAG_OPEN_DOMAIN: the pool-ordering entries take any int32 as an answer value
 ORDER_POOL, ORDER_SHUFFLED = 0, 1
 RULE_WEIGHT_SUM, RULE_BEST_OF = 0, 1
 STOP_DECIDED = 0x1

@@ -12,7 +12,7 @@ from math import comb
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes
+from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes, truth_codes
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 from .token_budget import orderings
 
@@ -114,7 +114,7 @@ def check_rules(cap, need, rule_flags, N: int):
 
 
 def adaptive_prefix(pool, truth, cap, need, rule_flags=None, tokens=None, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
-                    p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> AdaptiveResult:
+                    p_offset: int = 0, M: int | None = None, want_cells: bool = False, open_domain: bool = False) -> AdaptiveResult:
     """pool int32 [P, N], truth [P], cap int32 [B], need int32 [B, N + 1], rule_flags int32 [B] or None, tokens [P, N] or None.
     ``r_end=None``: pool order (one draw, r_begin must be 0); otherwise the shuffled orderings r in [r_begin, r_end).  ``M``: per_resample
     classes (None: not computed).  ``want_cells``: pool order only."""
@@ -153,18 +153,12 @@ def adaptive_prefix(pool, truth, cap, need, rule_flags=None, tokens=None, r_begi
         cells = np.zeros((P, B), dtype=CELL_DTYPE)
         cell_tokens = np.zeros((P, B), dtype=np.int64) if tok is not None else None
         cell_votes = np.zeros((P, B), dtype=np.int32)
-    codes, uniq, bad = dense_codes(pool)
+    codes, uniq, bad = dense_codes(pool, open_domain)
     err = (ERR_DOMAIN_BIT if bad else 0) | (ERR_RULE_FLAG_BIT if (flags & ~STOP_DECIDED).any() else 0)
     L = P * R
     if L == 0:
         return AdaptiveResult(P, R, tie, tsum, vsum, tcsum, hist, per, cells, cell_tokens, cell_votes, err)
-    tcode = np.full(P, -1, dtype=np.int64)
-    for p in range(P):
-        t = int(truth[p])
-        if 0 <= t < NUM_BINS:
-            k = np.searchsorted(uniq[p], t)
-            if k < len(uniq[p]) and uniq[p][k] == t:
-                tcode[p] = k
+    tcode = truth_codes(uniq, truth, open_domain)
     ns = np.arange(N + 1, dtype=np.int64)
     for l0 in range(0, L, LANE_BLOCK):
         l1 = min(L, l0 + LANE_BLOCK)
@@ -229,7 +223,7 @@ def adaptive_prefix(pool, truth, cap, need, rule_flags=None, tokens=None, r_begi
                 cells["max_count"][lp, b] = mx
                 cells["truth_count"][lp, b] = tc
                 cells["n_modes"][lp, b] = nm
-                cells["min_mode"][lp, b] = [int(uniq[p][c]) if n else -1 for p, c, n in zip(lp.tolist(), mc.tolist(), nb.tolist())]
+                cells["min_mode"][lp, b] = [(int(c) if open_domain else int(uniq[p][c])) if n else -1 for p, c, n in zip(lp.tolist(), mc.tolist(), nb.tolist())]
                 cells["hit"][lp, b] = hit
                 cell_votes[lp, b] = nb
                 if cell_tokens is not None:

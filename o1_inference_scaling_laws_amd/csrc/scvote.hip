@@ -1320,6 +1320,7 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
 template <class LdsWords>
 int launch_lane_body(scv_ctx* ctx, scv::ResampleFn fn, scv::ResampleArgs& a, LdsWords lds_words, const char* what, int64_t* stat_calls) {
     const int64_t P = a.P, R = a.R;
+    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;        // every lane body encodes its rows by the context's rule
     SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
     int best_lanes = 0, best_np = 0, best_per_cu = 0;
     size_t best_lds = 0;
@@ -1620,6 +1621,7 @@ int launch_expected(scv_ctx* ctx, const int32_t* pool, const int32_t* n_valid, c
     a.mode = scv::kResampleModeExpected;
     a.tab = ctx->d_expected_tab;
     a.score_out = score; a.hit_out = hit;
+    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;        // (its own launch: not through launch_lane_body)
     int64_t grid = (int64_t)ctx->num_cus * per_cu;
     if (grid > P) grid = P;
     if (ctx->grid_override > 0) grid = ctx->grid_override;

@@ -77,7 +77,7 @@ __device__ __forceinline__ void adaptive_run(const ResampleArgs& a, uint32_t* sm
         int64_t p_hi = (t0 + lanes - 1) / R;
         if (p_hi > a.P - 1) p_hi = a.P - 1;
         for (int64_t pl = wave; pl <= p_hi - p_lo; pl += nwaves) {                  // the error bits are raised where they are found: no lane carries them
-            const bool bad = resample_encode_row(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
+            const bool bad = resample_encode(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
             if (__ballot(bad) && lane == 0) atomicOr(a.err_flag, 1u);
         }
         __syncthreads();
@@ -115,7 +115,7 @@ __device__ __forceinline__ void adaptive_run(const ResampleArgs& a, uint32_t* sm
                 const int64_t cell = p * (int64_t)B + b;
                 if (a.cells_out) {
                     int32_t mm = -1;
-                    if (maxc) { mm = a.pool[p * (int64_t)N + min_x]; if ((uint32_t)mm >= (uint32_t)kBins) mm = kBins - 1; }
+                    if (maxc) mm = resample_min_mode(a, p, min_x, (uint32_t)my_row[min_x]);
                     uint32_t* cw = reinterpret_cast<uint32_t*>(a.cells_out) + 4 * cell;      // scv_cell: 4-byte aligned only
                     cw[0] = maxc;
                     cw[1] = tc;

@@ -97,6 +97,8 @@ struct ResampleArgs {
     int32_t* cell_votes_out;                             // [P, B] (NULL ok; pool order only), overwritten
     // the vote over draws with replacement (scv_iid_prefix_i32, scvote_iid.hip.h) adds no field: n_valid holds the draw budgets (not clamped
     // to N), tokens may be NULL
+    // appended for SCV_FLAG_OPEN_DOMAIN (every body): rows are encoded by resample_encode_row_open, min_mode is a code (scvote_resample.hip.h)
+    int32_t open_domain;
 };
 using ResampleFn = void (*)(const ResampleArgs);
 constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3,

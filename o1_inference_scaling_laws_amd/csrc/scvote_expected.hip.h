@@ -96,7 +96,7 @@ __device__ __forceinline__ void expected_majority_body(const ResampleArgs& a, ui
     bool bad = false;
     for (int64_t p = blockIdx.x; p < a.P; p += gridDim.x) {
         for (int i = tid; i < 256 + 260; i += (int)blockDim.x) cnt[i] = 0;          // cnt | hist
-        if (wave == 0) bad |= resample_encode_row(a, p, reinterpret_cast<uint8_t*>(codes), meta, scr, lane);
+        if (wave == 0) bad |= resample_encode(a, p, reinterpret_cast<uint8_t*>(codes), meta, scr, lane);
         __syncthreads();
         const uint8_t* cb = reinterpret_cast<const uint8_t*>(codes);
         for (int e = tid; e < N; e += (int)blockDim.x) atomicAdd(&cnt[cb[e]], 1);

@@ -75,7 +75,7 @@ __device__ __forceinline__ void iid_body(const ResampleArgs& a, uint32_t* smem) 
         int64_t p_hi = (t0 + lanes - 1) / R;
         if (p_hi > a.P - 1) p_hi = a.P - 1;
         for (int64_t pl = wave; pl <= p_hi - p_lo; pl += nwaves)
-            bad |= resample_encode_row(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
+            bad |= resample_encode(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
         __syncthreads();
         const int64_t t = t0 + tid;
         const bool live = t < total;

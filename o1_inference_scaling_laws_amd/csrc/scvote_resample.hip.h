@@ -48,23 +48,20 @@ __device__ __forceinline__ uint32_t resample_byte(uint32_t e, int lanes_log2, ui
     return ((e >> 2) << (lanes_log2 + 2)) + (e & 3u) + lane_byte;
 }
 
-// one wave re-encodes the pool row of problem p into value-ordered byte codes: row_codes (bytes), meta[0] = the truth's code or -1,
-// meta[1] = the number of distinct values.  scr: 64 words of the wave's own.  Returns true when a vote was outside 0..1023.
-__device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64_t p, uint8_t* row_codes, int32_t* meta, uint32_t* scr, int lane) {
-    const int N = a.N;
-    const int32_t* row = a.pool + p * (int64_t)N;
+// One wave turns up to 256 votes that lie in 0..1023 (v[k]: element lane + 64 k) into value-ordered byte codes: a 1024-bit presence map, its running
+// popcount and from them every vote's rank among the row's distinct values.  meta[0] = the code of t = truth_of() (evaluated by lane 0 only), or -1
+// when t is outside the bins or not in the row; meta[1] = the number of distinct values.  scr: 64 words of the wave's own.
+template <class TruthOf>
+__device__ __forceinline__ void resample_encode_binned(const int32_t (&v)[kResampleMaxN / 64], TruthOf truth_of, int N, uint8_t* row_codes, int32_t* meta,
+                                                       uint32_t* scr, int lane) {
     if (lane < 32) scr[lane] = 0u;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    int32_t v[kResampleMaxN / 64];
-    bool bad = false;
 #pragma unroll
     for (int k = 0; k < kResampleMaxN / 64; ++k) {
         const int e = lane + 64 * k;
-        int32_t x = e < N ? row[e] : 0;
-        if ((uint32_t)x >= (uint32_t)kBins) { bad = bad || e < N; x = kBins - 1; }
-        v[k] = x;
+        const int32_t x = v[k];
         if (e < N) atomicOr(&scr[x >> 5], 1u << (x & 31));
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -75,8 +72,8 @@ __device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64
     uint32_t incl = (uint32_t)__popc(word);
 #pragma unroll
     for (int d = 1; d < 32; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d, 64);
-        if ((lane & 31) >= d) incl += t;
+        const uint32_t u = (uint32_t)__shfl_up((int)incl, d, 64);
+        if ((lane & 31) >= d) incl += u;
     }
     if (lane < 32) scr[32 + lane] = incl - (uint32_t)__popc(word);
     const int32_t distinct = __shfl((int)incl, 31, 64);
@@ -92,14 +89,107 @@ __device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64
         }
     }
     if (lane == 0) {
-        const int32_t t = a.truth[p];
+        const int32_t t = truth_of();
         int32_t tcode = -1;
         if ((uint32_t)t < (uint32_t)kBins && ((scr[t >> 5] >> (t & 31)) & 1u))
             tcode = (int32_t)(scr[32 + (t >> 5)] + (uint32_t)__popc(scr[t >> 5] & ((1u << (t & 31)) - 1u)));
         meta[0] = tcode;
         meta[1] = distinct;
     }
+}
+
+// one wave re-encodes the pool row of problem p into value-ordered byte codes: row_codes (bytes), meta[0] = the truth's code or -1,
+// meta[1] = the number of distinct values.  scr: 64 words of the wave's own.  Returns true when a vote was outside 0..1023.
+__device__ __forceinline__ bool resample_encode_row(const ResampleArgs& a, int64_t p, uint8_t* row_codes, int32_t* meta, uint32_t* scr, int lane) {
+    const int N = a.N;
+    const int32_t* row = a.pool + p * (int64_t)N;
+    int32_t v[kResampleMaxN / 64];
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < kResampleMaxN / 64; ++k) {
+        const int e = lane + 64 * k;
+        int32_t x = e < N ? row[e] : 0;
+        if ((uint32_t)x >= (uint32_t)kBins) { bad = bad || e < N; x = kBins - 1; }
+        v[k] = x;
+    }
+    resample_encode_binned(v, [&] { return a.truth[p]; }, N, row_codes, meta, scr, lane);
     return bad;
+}
+
+// The same contract for SCV_FLAG_OPEN_DOMAIN: every int32 is a value of its own, ordered as signed integers; never a domain error (returns false).
+// Rank by counting, in registers: element j is broadcast from its lane (a readlane into a scalar register; j and N are uniform) and every lane
+// counts it against its own four keys, so after N steps lt[k] is the number of votes BELOW key k.  Equal keys have equal counts, a larger key a
+// larger one (it is above every vote the smaller key is above, and above that key itself), and every count is below N <= 256: the counts are an
+// order-preserving relabelling of the row INTO the bins, and the binned encoder makes them dense.  The truth takes the count of the vote it equals.
+// Per broadcast step, read from the gfx950 ISA: one v_readlane_b32 and, per register that holds votes, one v_cmp_lt_i32 and one add (a
+// v_addc_co_u32 that takes one compare as its carry and a second through a v_cndmask_b32): 3 / 5.1-5.3 / 7-7.8 / 9-10 VALU for 1 / 2 / 3 / 4
+// registers (192 per row at N = 64, ~660 at 128, ~2400 at 256).  No LDS beyond the binned encoder's 64 words.
+// one broadcast step: key j of register src goes to a scalar register, every lane counts it against its NK keys
+template <int NK>
+__device__ __forceinline__ void open_count_step(int32_t src, int jl, const int32_t (&key)[kResampleMaxN / 64], int32_t (&lt)[kResampleMaxN / 64]) {
+    const int32_t s = __builtin_amdgcn_readlane(src, jl);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) lt[k] += s < key[k] ? 1 : 0;
+}
+// lt[k] += votes below key[k], for the NK registers of a row of N votes, 64 (NK - 1) < N <= 64 NK.  Full registers take the loop of constant length,
+// which the compiler unrolls (the last one too when N = 64 NK: 64, 128, 192, 256); only a ragged last register takes the rolled one.
+template <int NK>
+__device__ __forceinline__ void open_count_below(const int32_t (&key)[kResampleMaxN / 64], int32_t (&lt)[kResampleMaxN / 64], int N) {
+    const int tail = N - 64 * (NK - 1);
+#pragma unroll
+    for (int kk = 0; kk < NK; ++kk) {
+        if (kk < NK - 1 || tail == 64) {
+            for (int jl = 0; jl < 64; ++jl) open_count_step<NK>(key[kk], jl, key, lt);
+        } else {
+            for (int jl = 0; jl < tail; ++jl) open_count_step<NK>(key[kk], jl, key, lt);
+        }
+    }
+}
+
+// Outlined, with its three LDS pointers as 32-bit LDS addresses: the bodies keep their register counts, and a flag-off launch never enters it.
+using lds_u8 = __attribute__((address_space(3))) uint8_t;
+using lds_i32 = __attribute__((address_space(3))) int32_t;
+using lds_u32 = __attribute__((address_space(3))) uint32_t;
+__device__ __noinline__ void resample_encode_row_open(const int32_t* row, int32_t t, int N_arg, lds_u8* row_codes_l, lds_i32* meta_l, lds_u32* scr_l) {
+    const int N = __builtin_amdgcn_readfirstlane(N_arg);                            // arguments of a real call arrive in VGPRs: N is uniform, say so
+    const int lane = (int)threadIdx.x & 63;
+    uint8_t* row_codes = (uint8_t*)row_codes_l;
+    int32_t* meta = (int32_t*)meta_l;
+    uint32_t* scr = (uint32_t*)scr_l;
+    int32_t key[kResampleMaxN / 64], lt[kResampleMaxN / 64];
+#pragma unroll
+    for (int k = 0; k < kResampleMaxN / 64; ++k) {
+        const int e = lane + 64 * k;
+        key[k] = e < N ? row[e] : 0;
+        lt[k] = 0;
+    }
+    const int nk = (N + 63) >> 6;                                                    // registers that hold a vote (scalar, like N)
+    if (nk == 1) open_count_below<1>(key, lt, N);
+    else if (nk == 2) open_count_below<2>(key, lt, N);
+    else if (nk == 3) open_count_below<3>(key, lt, N);
+    else open_count_below<4>(key, lt, N);
+    int32_t mine = -1;
+#pragma unroll
+    for (int k = 0; k < kResampleMaxN / 64; ++k)
+        if (lane + 64 * k < N && key[k] == t) mine = lt[k];
+    const unsigned long long has = __ballot(mine >= 0);
+    const int32_t tl = has ? __shfl(mine, __ffsll(has) - 1, 64) : -1;
+    resample_encode_binned(lt, [&] { return tl; }, N, row_codes, meta, scr, lane);
+}
+
+// the encoder of a context: open_domain is uniform over the launch
+__device__ __forceinline__ bool resample_encode(const ResampleArgs& a, int64_t p, uint8_t* row_codes, int32_t* meta, uint32_t* scr, int lane) {
+    if (a.open_domain) { resample_encode_row_open(a.pool + p * (int64_t)a.N, a.truth[p], a.N, (lds_u8*)row_codes, (lds_i32*)meta, (lds_u32*)scr); return false; }
+    return resample_encode_row(a, p, row_codes, meta, scr, lane);
+}
+
+// min_mode of a pool-order cell (token-budget, weighted, adaptive bodies): x is a sample of the smallest modal value, code its byte code.  The
+// value itself, clamped into the bins; under SCV_FLAG_OPEN_DOMAIN the code (an int16 cannot hold an arbitrary int32).
+__device__ __forceinline__ int32_t resample_min_mode(const ResampleArgs& a, int64_t p, uint32_t x, uint32_t code) {
+    if (a.open_domain) return (int32_t)code;
+    int32_t mm = a.pool[p * (int64_t)a.N + x];
+    if ((uint32_t)mm >= (uint32_t)kBins) mm = kBins - 1;
+    return mm;
 }
 
 }  // namespace scv
@@ -174,7 +264,7 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
         int64_t p_hi = (t0 + lanes - 1) / R;
         if (p_hi > a.P - 1) p_hi = a.P - 1;
         for (int64_t pl = wave; pl <= p_hi - p_lo; pl += nwaves)
-            bad |= resample_encode_row(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
+            bad |= resample_encode(a, p_lo + pl, reinterpret_cast<uint8_t*>(rows + pl * N4), meta + 2 * pl, scr + 64 * wave, lane);
         __syncthreads();
         const int64_t t = t0 + tid;
         const bool live = t < total;

@@ -74,7 +74,7 @@ __device__ __forceinline__ void weighted_run(const ResampleArgs& a, uint32_t* sm
         if (p_hi > a.P - 1) p_hi = a.P - 1;
         for (int64_t pl = wave; pl <= p_hi - p_lo; pl += nwaves) {
             uint32_t* rw = rows + pl * RW;
-            bad |= resample_encode_row(a, p_lo + pl, reinterpret_cast<uint8_t*>(rw), meta + 2 * pl, scr + 64 * wave, lane);
+            bad |= resample_encode(a, p_lo + pl, reinterpret_cast<uint8_t*>(rw), meta + 2 * pl, scr + 64 * wave, lane);
             const int32_t* wrow = a.weights + (p_lo + pl) * (int64_t)N;
             // Word e takes the place of bytes 4 e .. 4 e + 3: the elements go from the top down, so that a word never lands on a byte code
             // that is still to be read (elements 64 k .. 64 k + 63 become bytes 256 k .. 256 k + 255, at or above every element below them),
@@ -169,7 +169,7 @@ __device__ __forceinline__ void weighted_run(const ResampleArgs& a, uint32_t* sm
                         const int64_t cell = p * (int64_t)B + b;
                         if (a.cells_out) {
                             int32_t mm = -1;
-                            if (top) { mm = a.pool[p * (int64_t)N + min_x]; if ((uint32_t)mm >= (uint32_t)kBins) mm = kBins - 1; }
+                            if (top) mm = resample_min_mode(a, p, min_x, min_code);
                             uint32_t* cw = reinterpret_cast<uint32_t*>(a.cells_out) + 4 * cell;
                             cw[0] = top;
                             cw[1] = tw;

@@ -136,14 +136,21 @@ def pinned_empty(shape, dtype=np.int32) -> np.ndarray:
 class Engine:
     """One context per GPU per process (one process per GPU under torch.distributed)."""
 
-    def __init__(self, device: int | None = None, timing: bool = False, clamp_to_invalid_bin: bool = False, packed_cells: bool = False, _adopt=None):
-        """``packed_cells=True`` (SCV_FLAG_PACKED_CELLS, opt-in): ``aggregate_device`` over cells of up to 127 votes writes 4-byte records --
+    def __init__(self, device: int | None = None, timing: bool = False, clamp_to_invalid_bin: bool = False, packed_cells: bool = False, _adopt=None,
+                 open_domain: bool = False):
+        """``open_domain=True`` (SCV_FLAG_OPEN_DOMAIN, opt-in): the six pool-ordering calls (resample, expected, token budget, weighted, adaptive,
+        iid) take any int32 as an answer value -- no domain error, no clamp -- and the ``min_mode`` of their pool-order cells is the CODE of the
+        smallest modal value (``decode_min_mode`` gives the value).  The dense calls keep the 1024 bins.
+
+        ``packed_cells=True`` (SCV_FLAG_PACKED_CELLS, opt-in): ``aggregate_device`` over cells of up to 127 votes writes 4-byte records --
         its ``cells`` tensor is uint8 [P, B, 4] and ``cells_from_torch`` decodes it (``unpack_cells``); every other call form of such an engine
         must be made without a cell table (``cells=False``)."""
         self._L = _lib.load()            # raises ImportError when csrc/libscvote.so is missing
         self._ctx = C.c_void_p()
         self.packed_cells = bool(packed_cells)
-        flags = (_lib.FLAG_TIMING if timing else 0) | (_lib.FLAG_CLAMP if clamp_to_invalid_bin else 0) | (_lib.FLAG_PACKED_CELLS if packed_cells else 0)
+        flags = (_lib.FLAG_TIMING if timing else 0) | (_lib.FLAG_CLAMP if clamp_to_invalid_bin else 0) | (_lib.FLAG_PACKED_CELLS if packed_cells else 0) | \
+            (_lib.FLAG_OPEN_DOMAIN if open_domain else 0)
+        self.open_domain = bool(open_domain)
         if device is None:
             import torch
             device = torch.cuda.current_device() if torch.cuda.is_available() else -1
@@ -776,7 +783,7 @@ class MultiDeviceEngine:
     a one-shot all-reduce over xGMI peer access (default), or RCCL single-process (``rccl=True``; distinct devices).
     """
 
-    def __init__(self, devices=None, rccl: bool = False, timing: bool = False, clamp_to_invalid_bin: bool = False):
+    def __init__(self, devices=None, rccl: bool = False, timing: bool = False, clamp_to_invalid_bin: bool = False, open_domain: bool = False):
         L = _lib.load()
         if devices is None:
             n = L.scv_device_count()
@@ -786,7 +793,7 @@ class MultiDeviceEngine:
         devices = [int(d) for d in devices]
         self._L = L
         self._comm = C.c_void_p()
-        flags = (_lib.FLAG_TIMING if timing else 0) | (_lib.FLAG_CLAMP if clamp_to_invalid_bin else 0)
+        flags = (_lib.FLAG_TIMING if timing else 0) | (_lib.FLAG_CLAMP if clamp_to_invalid_bin else 0) | (_lib.FLAG_OPEN_DOMAIN if open_domain else 0)
         arr = (C.c_int * len(devices))(*devices)
         self.fell_back_to_rccl = False
         try:
@@ -804,7 +811,8 @@ class MultiDeviceEngine:
             rccl = True
             self.fell_back_to_rccl = True
         self.rccl = bool(rccl)
-        self.engines = [Engine(device=d, timing=timing, clamp_to_invalid_bin=clamp_to_invalid_bin, _adopt=L.scv_comm_ctx(self._comm, r))
+        self.engines = [Engine(device=d, timing=timing, clamp_to_invalid_bin=clamp_to_invalid_bin, open_domain=open_domain,
+                               _adopt=L.scv_comm_ctx(self._comm, r))
                         for r, d in enumerate(devices)]
 
     def close(self):
@@ -1031,6 +1039,21 @@ def unpack_cells(packed_u32: np.ndarray) -> np.ndarray:
     mm = ((w >> 21) & 0x3FF).astype(np.int16)
     out["min_mode"] = np.where(out["max_count"] == 0, np.int16(-1), mm)
     out["hit"] = (w >> 31).astype(np.uint8)
+    return out
+
+
+def decode_min_mode(pool, cells) -> np.ndarray:
+    """The ``min_mode`` of pool-order cells written under SCV_FLAG_OPEN_DOMAIN (``Engine(open_domain=True)``; the mirrors with
+    ``open_domain=True``) is a code: the rank of the smallest modal value among the distinct values of its row ``pool[p, 0:N]``, in ascending
+    signed order, or -1 for the empty cell.  pool int32 [P, N], cells CELL_DTYPE [P, B] -> int64 [P, B]: the values (-1 for the empty cell;
+    tell it from a modal value -1 by ``max_count == 0``)."""
+    pool = np.asarray(pool)
+    codes = np.asarray(cells["min_mode"], dtype=np.int64)
+    out = np.full(codes.shape, -1, dtype=np.int64)
+    for p in range(codes.shape[0]):
+        u = np.unique(pool[p].astype(np.int32))
+        ok = codes[p] >= 0
+        out[p, ok] = u[codes[p, ok]]
     return out
 
 

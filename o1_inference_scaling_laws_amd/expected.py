@@ -64,24 +64,27 @@ def _check(pool, truth, n_valid):
     return pool, truth, np.clip(nv, 0, N), N
 
 
-def row_classes(row, truth: int):
+def row_classes(row, truth: int, open_domain: bool = False):
     """(c_t, [c_v for v != t]) of one pool row: votes outside 0..1023 count as 1023; a truth outside the bins has c_t = 0 and every
-    value is an 'other' class."""
+    value is an 'other' class.  ``open_domain`` (SCV_FLAG_OPEN_DOMAIN): every integer is a value of its own, the truth included."""
     v = np.asarray(row, dtype=np.int64)
-    v = np.where((v < 0) | (v >= NUM_BINS), NUM_BINS - 1, v)
+    if not open_domain:
+        v = np.where((v < 0) | (v >= NUM_BINS), NUM_BINS - 1, v)
     vals, counts = np.unique(v, return_counts=True)
     ct = 0
     others = []
     for x, c in zip(vals.tolist(), counts.tolist()):
-        if x == truth and 0 <= truth < NUM_BINS:
+        if x == truth and (open_domain or 0 <= truth < NUM_BINS):
             ct = c
         else:
             others.append(c)
     return ct, others
 
 
-def domain_error(pool) -> bool:
-    """Error bit 0 of the call: a vote outside 0..1023."""
+def domain_error(pool, open_domain: bool = False) -> bool:
+    """Error bit 0 of the call: a vote outside 0..1023 (never under ``open_domain``)."""
+    if open_domain:
+        return False
     v = np.asarray(pool, dtype=np.int64)
     return bool(((v < 0) | (v >= NUM_BINS)).any())
 
@@ -144,13 +147,13 @@ def _exact_row(N: int, ct: int, others, ks):
     return E, H
 
 
-def expected_majority_exact(pool, truth, n_valid):
+def expected_majority_exact(pool, truth, n_valid, open_domain: bool = False):
     """(E, H): lists [P][B] of fractions.Fraction -- the expected score (1 / n_modes on a hit) and the hit probability of the majority vote
     over a uniformly random k_b-subset of pool[p], k_b = clamp(n_valid[b], 0, N)."""
     pool, truth, ks, N = _check(pool, truth, n_valid)
     E, H = [], []
     for p in range(pool.shape[0]):
-        ct, others = row_classes(pool[p], int(truth[p]))
+        ct, others = row_classes(pool[p], int(truth[p]), open_domain)
         e, h = _exact_row(N, ct, others, [int(k) for k in ks])
         E.append(e)
         H.append(h)
@@ -213,7 +216,7 @@ def item_fp64_ops(N: int, ct: int, others, kmax: int, hit: bool = True) -> int:
     return sum(2 * 256 * (j + 1) * len(big) for j, _y, _w, _kind, _L, big in work_items(N, ct, others, kmax, hit))
 
 
-def expected_majority_quadrature(pool, truth, n_valid, hit: bool = True):
+def expected_majority_quadrature(pool, truth, n_valid, hit: bool = True, open_domain: bool = False):
     """The GPU's algorithm in numpy float64: (score [P, B], hit_prob [P, B] or None)."""
     pool, truth, ks, N = _check(pool, truth, n_valid)
     P, B = pool.shape[0], ks.shape[0]
@@ -221,7 +224,7 @@ def expected_majority_quadrature(pool, truth, n_valid, hit: bool = True):
     score = np.zeros((P, B))
     hitp = np.zeros((P, B)) if hit else None
     for p in range(P):
-        ct, others = row_classes(pool[p], int(truth[p]))
+        ct, others = row_classes(pool[p], int(truth[p]), open_domain)
         mo = max(others, default=0)
         acc_e = np.zeros(B)
         acc_h = np.zeros(B)

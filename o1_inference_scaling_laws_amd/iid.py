@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, ResampleResult, dense_codes
+from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, ResampleResult, dense_codes, truth_codes
 from .synth import G, _MASK32, mix64
 
 SEED_SALT = np.uint64(0xA0761D6478BD642F)
@@ -29,7 +29,7 @@ def draw_index(s, r, i: int, N: int):
     return ((u >> np.uint64(32)) & _MASK32) * np.uint64(N) >> np.uint64(32)
 
 
-def iid_prefix(pool, truth, n_draws, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0, M: int = 0) -> ResampleResult:
+def iid_prefix(pool, truth, n_draws, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0, M: int = 0, open_domain: bool = False) -> ResampleResult:
     """pool int32 [P, N], truth int32 [P], n_draws int32 [B] (budget b votes over the first max(n_draws[b], 0) draws with replacement;
     not clamped to N, at most MAX_DRAWS), resamples [r_begin, r_end).  ``M``: per_resample classes (0: not computed).  A budget above
     MAX_DRAWS returns all-zero outputs with ERR_DRAWS_BIT in ``error_bits`` (what a DEVICE-mode call leaves; a HOST-mode call refuses)."""
@@ -55,15 +55,9 @@ def iid_prefix(pool, truth, n_draws, r_begin: int, r_end: int, seed: int, tokens
         return ResampleResult(P, R, tie, tsum, tcsum, per, 0)
     if ks.max() > MAX_DRAWS:
         return ResampleResult(P, R, tie, tsum, tcsum, per, ERR_DRAWS_BIT)
-    codes, uniq, bad = dense_codes(pool)
+    codes, uniq, bad = dense_codes(pool, open_domain)
     err = ERR_DOMAIN_BIT if bad else 0
-    tcode = np.full(P, -1, dtype=np.int64)                           # the truth's code in its row, or -1 (absent / outside the bins: never hits)
-    for p in range(P):
-        t = int(truth[p])
-        if 0 <= t < NUM_BINS:
-            k = np.searchsorted(uniq[p], t)
-            if k < len(uniq[p]) and uniq[p][k] == t:
-                tcode[p] = k
+    tcode = truth_codes(uniq, truth, open_domain)
     lp = np.repeat(np.arange(P), R)                                  # lanes problem-major
     lr = np.tile(np.arange(r_begin, r_end, dtype=np.int64), P)
     s = problem_streams(seed, p_offset + lp)

@@ -62,11 +62,16 @@ class ResampleResult:
         return (self.per_resample[:, b, 1:] / m).sum(axis=1) / self.P
 
 
-def dense_codes(pool: np.ndarray):
+def dense_codes(pool: np.ndarray, open_domain: bool = False):
     """Votes outside 0..1023 -> bin 1023 (and a flag); then each row re-encoded to value-ordered dense codes.
-    Returns (codes int64 [P, N], distinct values per row [P], sorted distinct values per row (list), domain flag)."""
+    Returns (codes int64 [P, N], distinct values per row [P], sorted distinct values per row (list), domain flag).
+    ``open_domain`` (SCV_FLAG_OPEN_DOMAIN): every int32 is a value of its own, in signed order -- no clamp, never a domain flag."""
     v = np.asarray(pool, dtype=np.int64)
-    bad = (v < 0) | (v >= NUM_BINS)
+    if open_domain:
+        v = np.asarray(pool).astype(np.int32).astype(np.int64)
+        bad = np.zeros(v.shape, dtype=bool)
+    else:
+        bad = (v < 0) | (v >= NUM_BINS)
     v = np.where(bad, NUM_BINS - 1, v)
     codes = np.empty_like(v)
     uniq = []
@@ -77,8 +82,21 @@ def dense_codes(pool: np.ndarray):
     return codes, uniq, bool(bad.any())
 
 
+def truth_codes(uniq, truth, open_domain: bool = False) -> np.ndarray:
+    """The truth's code in its row (``uniq``: the rows' sorted distinct values, from dense_codes), or -1: absent, or -- without
+    ``open_domain`` -- outside the bins (such a truth never hits)."""
+    tcode = np.full(len(uniq), -1, dtype=np.int64)
+    for p, u in enumerate(uniq):
+        t = int(truth[p])
+        if open_domain or 0 <= t < NUM_BINS:
+            k = np.searchsorted(u, t)
+            if k < len(u) and u[k] == t:
+                tcode[p] = k
+    return tcode
+
+
 def resample_prefix(pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
-                    M: int | None = None) -> ResampleResult:
+                    M: int | None = None, open_domain: bool = False) -> ResampleResult:
     """pool int32 [P, N], truth int32 [P], n_valid int32 [B] (budget b votes over the first clamp(n_valid[b], 0, N) of a
     random ordering), resamples [r_begin, r_end).  ``M``: per_resample classes (None: not computed)."""
     pool = np.asarray(pool)
@@ -98,19 +116,12 @@ def resample_prefix(pool, truth, n_valid, r_begin: int, r_end: int, seed: int, t
     tsum = np.zeros(B, dtype=np.int64)
     tcsum = np.zeros(B, dtype=np.int64)
     per = np.zeros((R, B, M), dtype=np.int64) if M is not None else None
-    codes, uniq, bad = dense_codes(pool)
+    codes, uniq, bad = dense_codes(pool, open_domain)
     err = ERR_DOMAIN_BIT if bad else 0
     L = P * R
     if L == 0:
         return ResampleResult(P, R, tie, tsum, tcsum, per, err)
-    # the truth's code in its row, or -1 (absent; a truth outside the bins never hits)
-    tcode = np.full(P, -1, dtype=np.int64)
-    for p in range(P):
-        t = int(truth[p])
-        if 0 <= t < NUM_BINS:
-            k = np.searchsorted(uniq[p], t)
-            if k < len(uniq[p]) and uniq[p][k] == t:
-                tcode[p] = k
+    tcode = truth_codes(uniq, truth, open_domain)
     lp = np.repeat(np.arange(P), R)                                  # lanes problem-major
     lr = np.tile(np.arange(r_begin, r_end, dtype=np.int64), P)
     s = problem_streams(seed, p_offset + lp)

@@ -8,7 +8,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes, problem_streams, swap_index
+from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes, truth_codes, problem_streams, swap_index
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
 ORDER_POOL, ORDER_SHUFFLED = 0, 1
@@ -71,7 +71,7 @@ def orderings(P: int, N: int, r_begin: int, r_end: int, seed: int, p_offset: int
 
 
 def token_budget_prefix(pool, tokens, truth, token_budgets, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
-                        p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> TokenBudgetResult:
+                        p_offset: int = 0, M: int | None = None, want_cells: bool = False, open_domain: bool = False) -> TokenBudgetResult:
     """pool / tokens int32 [P, N], truth [P], token_budgets int64 [B].  ``r_end=None``: pool order (one draw, r_begin must be 0); otherwise
     the shuffled orderings r in [r_begin, r_end).  ``M``: per_resample classes (None: not computed).  ``want_cells``: pool order only."""
     pool = np.asarray(pool)
@@ -104,18 +104,12 @@ def token_budget_prefix(pool, tokens, truth, token_budgets, r_begin: int = 0, r_
         from .engine import CELL_DTYPE
         cells = np.zeros((P, B), dtype=CELL_DTYPE)
         cell_tokens = np.zeros((P, B), dtype=np.int64)
-    codes, uniq, bad = dense_codes(pool)
+    codes, uniq, bad = dense_codes(pool, open_domain)
     err = (ERR_DOMAIN_BIT if bad else 0) | (ERR_TOKEN_BIT if (tok < 0).any() else 0)
     L = P * R
     if L == 0:
         return TokenBudgetResult(P, R, tie, tsum, vsum, tcsum, per, cells, cell_tokens, err)
-    tcode = np.full(P, -1, dtype=np.int64)
-    for p in range(P):
-        t = int(truth[p])
-        if 0 <= t < NUM_BINS:
-            k = np.searchsorted(uniq[p], t)
-            if k < len(uniq[p]) and uniq[p][k] == t:
-                tcode[p] = k
+    tcode = truth_codes(uniq, truth, open_domain)
     for l0 in range(0, L, LANE_BLOCK):
         l1 = min(L, l0 + LANE_BLOCK)
         lanes = np.arange(l0, l1)
@@ -170,7 +164,7 @@ def token_budget_prefix(pool, tokens, truth, token_budgets, r_begin: int = 0, r_
                 cells["max_count"][lp, b] = mx
                 cells["truth_count"][lp, b] = tc
                 cells["n_modes"][lp, b] = nm
-                cells["min_mode"][lp, b] = [int(uniq[p][k]) if k >= 0 else -1 for p, k in zip(lp.tolist(), mc.tolist())]
+                cells["min_mode"][lp, b] = [(int(k) if open_domain else int(uniq[p][k])) if k >= 0 else -1 for p, k in zip(lp.tolist(), mc.tolist())]
                 cells["hit"][lp, b] = hit
                 cell_tokens[lp, b] = S[rows, nb]
     return TokenBudgetResult(P, R, tie, tsum, vsum, tcsum, per, cells, cell_tokens, err)

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes
+from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes, truth_codes
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 from .token_budget import orderings
 
@@ -71,7 +71,7 @@ def quantize_weights(scores, lo=None, hi=None) -> np.ndarray:
 
 
 def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
-                    p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False) -> WeightedResult:
+                    p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False, open_domain: bool = False) -> WeightedResult:
     """pool / weights int32 [P, N], truth [P], n_valid int32 [B].  ``r_end=None``: pool order (one draw, r_begin must be 0); otherwise the
     shuffled orderings r in [r_begin, r_end).  ``M``: per_resample classes (None: not computed).  ``want_cells``: pool order only."""
     pool = np.asarray(pool)
@@ -110,20 +110,14 @@ def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, 
         cells = np.zeros((P, B), dtype=CELL_DTYPE)
         cells["min_mode"] = -1
         cell_tokens = np.zeros((P, B), dtype=np.int64) if tok is not None else None
-    codes, uniq, bad = dense_codes(pool)
+    codes, uniq, bad = dense_codes(pool, open_domain)
     wbad = (wts < 0) | (wts > WEIGHT_MAX)
     err = (ERR_DOMAIN_BIT if bad else 0) | (ERR_WEIGHT_BIT if wbad.any() else 0)
     wts = wts & WEIGHT_MAX                                              # what the kernel counts after it raised the bit (results are invalid)
     L = P * R
     if L == 0:
         return WeightedResult(P, R, tie, tsum, per, cells, cell_tokens, err)
-    tcode = np.full(P, -1, dtype=np.int64)
-    for p in range(P):
-        t = int(truth[p])
-        if 0 <= t < NUM_BINS:
-            k = np.searchsorted(uniq[p], t)
-            if k < len(uniq[p]) and uniq[p][k] == t:
-                tcode[p] = k
+    tcode = truth_codes(uniq, truth, open_domain)
     for l0 in range(0, L, LANE_BLOCK):
         l1 = min(L, l0 + LANE_BLOCK)
         lanes = np.arange(l0, l1)
@@ -166,7 +160,7 @@ def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, 
                 cells["max_count"][lp, b] = top
                 cells["truth_count"][lp, b] = tw
                 cells["n_modes"][lp, b] = nm
-                cells["min_mode"][lp, b] = [int(uniq[p][c]) if c >= 0 else -1 for p, c in zip(lp.tolist(), mc.tolist())]
+                cells["min_mode"][lp, b] = [(int(c) if open_domain else int(uniq[p][c])) if c >= 0 else -1 for p, c in zip(lp.tolist(), mc.tolist())]
                 cells["hit"][lp, b] = hit
                 if cell_tokens is not None:
                     cell_tokens[lp, b] = spent
