@@ -57,15 +57,16 @@ extern "C" {
                                       shapes (csrc/scvote_plan.h packed_ok).  Without a cell table every kernel serves such a context.  Decoder:
                                       o1_inference_scaling_laws_amd/engine.py unpack_cells */
 
-#define SCV_FLAG_OPEN_DOMAIN 0x8u /* OPT-IN: the six pool-ordering entries (scv_resample_prefix_i32, scv_expected_majority_i32, scv_token_budget_prefix_i32,
-                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32) take ANY int32 as an answer value: negative
+#define SCV_FLAG_OPEN_DOMAIN 0x8u /* OPT-IN: the pool-ordering entries (scv_resample_prefix_i32, scv_expected_majority_i32, scv_token_budget_prefix_i32,
+                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32, and scv_shortest_prefix_i32, which reaches
+                                      the same row encoder and whose cells_out[..].min_mode is then the CODE) take ANY int32 as an answer value: negative
                                       numbers, large integers, 32-bit hashes of normalised answer strings.  Two votes are the same value only when
                                       the integers are equal.  A vote's code is the rank of its value among the distinct values of the whole row
                                       pool[p, 0:N] in ascending SIGNED order -- what the byte codes of these entries already are for rows inside
                                       0..1023 -- and everything downstream walks codes, so nothing else changes: the permutation for (seed, pg, r),
                                       the draw streams, the token sums; slices of r and shards of p still add up bit for bit; HOST mode and hipGraph
                                       capture work as without the flag.  The truth hits exactly when it equals a modal value, whatever its
-                                      magnitude.  Under the flag these six entries never set error bit 0 (no SCV_ERR_DOMAIN), and
+                                      magnitude.  Under the flag these entries never set error bit 0 (no SCV_ERR_DOMAIN), and
                                       SCV_FLAG_CLAMP_TO_INVALID_BIN has no effect on them; every other error bit (1, 4, 5, 6, 7, 8) keeps its meaning.
                                       cells_out[..].min_mode (SCV_ORDER_POOL calls of the token-budget, weighted and adaptive entries) is then the
                                       CODE of the smallest modal value, 0 .. distinct - 1, or -1 for the empty cell -- not the value, which an
@@ -368,6 +369,55 @@ int scv_token_budget_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t
                                 int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out);
 
 /*
+ * short-m@k: the majority vote over the m SHORTEST of the first k samples of a pool ordering (new semantics, not in the reference): k samples
+ * are launched in parallel, the m that finish first vote, and the others are cut off when the m-th finishes.
+ *   pool / tokens  int32 [P, N] (both required; a negative token count is an error); n_valid / m_keep int32 [B] (both required, any order,
+ *   duplicates fine); truth int32 [P]
+ * For problem p (global index pg = p_offset + p), an ordering pi and budget b:
+ *   k_b = clamp(n_valid[b], 0, N), m_b = clamp(m_keep[b], 0, k_b)
+ *   S   = the first k_b samples of pi
+ *   V   = the m_b elements of S that come first when S is sorted ascending by the pair (tokens, pool index); the pool-index tie-break makes
+ *         V a function of the SET S, not of the order inside it
+ *   cell (p, pi, b) = statistics.multimode over the votes of V, scored as everywhere (1 / n_modes on a hit); m_b = 0 gives the empty cell:
+ *         no hit, and 0 in every sum
+ *   order  SCV_ORDER_POOL (0): pi is the identity (one draw): r_begin = 0, r_end = 1 required
+ *          SCV_ORDER_SHUFFLED (1): pi is EXACTLY the partial Fisher-Yates permutation of scv_resample_prefix_i32 for (seed, pg, r),
+ *          r in [r_begin, r_end)
+ * Votes and truths follow scv_resample_prefix_i32: a vote outside 0..1023 sets error bit 0 (SCV_ERR_DOMAIN at the call in HOST mode, at
+ * scv_sync in DEVICE mode) or counts as 1023 under SCV_FLAG_CLAMP_TO_INVALID_BIN; a truth outside the bins never hits.  A negative token
+ * count sets error bit 4: SCV_ERR_ARG at the call in HOST mode, at scv_sync in DEVICE mode.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own (no domain error, no clamp) and cells_out[..].min_mode is the CODE of the smallest modal value.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a budget; t_(m) is the token count of the last element of V (0 when m_b = 0):
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m (scoring.py: accuracy / exact rational)
+ *   voted_token_sum_out  int64 [B]        (NULL ok) sum over V of tokens
+ *   spent_token_sum_out  int64 [B]        (NULL ok) sum over V of tokens + (k_b - m_b) * t_(m): every sample not kept is cut off when the
+ *                        m-th finishes; the arithmetic is int64
+ *   latency_sum_out      int64 [B]        (NULL ok) sum of t_(m)
+ *   truth_count_sum_out  int64 [B]        (NULL ok) kept votes equal to the truth
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) class counts per ordering, summed over problems only (m < M; a hit with
+ *                        n_modes >= M sets error bit 1: SCV_ERR_ARG at scv_sync)
+ *   cells_out            scv_cell [P, B] (NULL ok; SCV_ORDER_POOL only) and cell_tokens_out int64 [P, B] (NULL ok; SCV_ORDER_POOL
+ *                        only; the cell's spent tokens): OVERWRITTEN in both modes
+ * Identities: with m_b >= k_b the call is scv_resample_prefix_i32 with tokens, bit for bit (tie classes, truth counts, voted = spent = its
+ * token sum; the latency is the largest token count of the prefix); with k_b = N the cell does not depend on the ordering; with all tokens
+ * equal V is the m_b lowest pool indices of S.
+ * DEVICE mode ACCUMULATES into the per-budget outputs and per_resample (+=) and only enqueues: one launch, no allocation, no
+ * synchronisation, legal under hipGraph capture.  HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices
+ * of r and shards of p (p_offset) add up to the whole call bit for bit.  Limits: 1 <= N <= 256, 1 <= B <= 32, 0 <= r_begin <= r_end,
+ * p_offset >= 0, M >= 1 when per_resample_out is given; anything else -- a bad order, SCV_ORDER_POOL with r-range other than [0, 1), cell
+ * outputs with SCV_ORDER_SHUFFLED -- is SCV_ERR_ARG.  One lane per (problem, ordering): a shuffle step sets one bit of the lane's bitmap over
+ * token ranks, a boundary walks its first m_b set bits (csrc/scvote_shortest.hip.h).
+ */
+int scv_shortest_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens,
+                            const int32_t* n_valid, const int32_t* m_keep, const int32_t* truth,
+                            int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                            int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                            int64_t* tie_class_hits_out, int64_t* voted_token_sum_out,
+                            int64_t* spent_token_sum_out, int64_t* latency_sum_out,
+                            int64_t* truth_count_sum_out, int64_t* per_resample_out,
+                            scv_cell* cells_out, int64_t* cell_tokens_out);
+
+/*
  * Weighted majority vote and best-of-N over the prefixes of a pool ordering (new semantics, not in the reference, whose every rule counts a
  * sample once: statistics.multimode, o1.py:202-213).  Each sample votes with an integer weight -- a verifier or reward-model score, a
  * confidence, quantised by the caller (o1_inference_scaling_laws_amd/weighted.py: quantize_weights).
@@ -538,7 +588,7 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
 
 /*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 7: a draw budget above SCV_IID_MAX_DRAWS in a DEVICE-mode scv_iid_prefix_i32, which then computed nothing; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32 or scv_shortest_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 7: a draw budget above SCV_IID_MAX_DRAWS in a DEVICE-mode scv_iid_prefix_i32, which then computed nothing; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the

@@ -823,7 +823,7 @@ int check_err_word(scv_ctx* ctx, uint32_t w) {
     if ((w & 1u) && !(ctx->flags & SCV_FLAG_CLAMP_TO_INVALID_BIN))
         return fail(SCV_ERR_DOMAIN, "a vote outside bins 0..1023 was seen; results are invalid");
     if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap / resample: a hit had n_modes >= M");
-    if (w & 16u) return fail(SCV_ERR_ARG, "token_budget: a token count was negative; results are invalid");
+    if (w & 16u) return fail(SCV_ERR_ARG, "token_budget / shortest: a token count was negative; results are invalid");
     if (w & 32u) return fail(SCV_ERR_ARG, "weighted: a weight was outside 0..%d; results are invalid", SCV_WEIGHT_MAX);
     if (w & 64u) return fail(SCV_ERR_ARG, "adaptive: a rule flag had a bit other than SCV_STOP_DECIDED; results are invalid");
     if (w & 128u) return fail(SCV_ERR_ARG, "iid: a draw budget was above SCV_IID_MAX_DRAWS = %d; nothing was computed", SCV_IID_MAX_DRAWS);
@@ -1312,7 +1312,7 @@ int aggregate_common(scv_ctx* ctx, bool prefix, const int32_t* answers, const in
 
 
 // One launch of a lane-per-(problem, ordering) body of scv_resample_prefix (the shuffle, scvote_resample.hip.h; the token budgets,
-// scvote_budget.hip.h; the weights, scvote_weighted.hip.h; the stopping rules, scvote_adaptive.hip.h): a.P, a.R, a.N, a.B and the body's fields
+// scvote_budget.hip.h; the weights, scvote_weighted.hip.h; the stopping rules, scvote_adaptive.hip.h; short-m@k, scvote_shortest.hip.h): a.P, a.R, a.N, a.B and the body's fields
 // are set by the caller, a.np_max here.  Workgroups of 256 / 128 / 64 lanes:
 // the one that keeps the most waves resident per CU (LDS: lds_words(lanes, rows a chunk touches) words -- the lanes' byte arrays, the
 // problem rows, the per-budget tables), the larger on a tie (fewer tables to flush).  Persistent grid.  `what` prefixes the error message;
@@ -1436,6 +1436,25 @@ int launch_adaptive(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, co
                             [&](int lanes, int np) { return scv::adaptive_lds_words((int)N, B, lanes, np, shuffled); }, "adaptive", nullptr);
 }
 
+// scv_shortest_prefix_i32 on device pointers: one launch of the short-m@k body of scv_resample_prefix<true> (scvote_shortest.hip.h),
+// accumulating into the per-budget outputs and overwriting the cells.
+int launch_shortest(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* m_keep, const int32_t* truth,
+                    int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                    int64_t* tie, int64_t* voted_sum, int64_t* spent_sum, int64_t* latency_sum, int64_t* truth_sum, int64_t* per_resample,
+                    scv_cell* cells, int64_t* cell_tokens, uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    const bool shuffled = order == SCV_ORDER_SHUFFLED;
+    scv::ResampleArgs a = lane_args(pool, tokens, n_valid, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie, voted_sum, truth_sum,
+                                    per_resample, err);
+    a.mode = scv::kResampleModeShortest;
+    a.m_keep = m_keep;
+    a.spent_sum = reinterpret_cast<unsigned long long*>(spent_sum);
+    a.latency_sum = reinterpret_cast<unsigned long long*>(latency_sum);
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
+    return launch_lane_body(ctx, pick_resample_kernel(true), a,
+                            [&](int lanes, int np) { return scv::shortest_lds_words((int)N, B, lanes, np, shuffled); }, "shortest", nullptr);
+}
+
 // scv_iid_prefix_i32 on device pointers: one launch of the draws-with-replacement body of scv_resample_prefix<false> (scvote_iid.hip.h),
 // accumulating into the outputs.
 int launch_iid(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_draws, const int32_t* truth,
@@ -1449,8 +1468,8 @@ int launch_iid(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const i
                             [&](int lanes, int np) { return scv::iid_lds_words((int)N, B, lanes, np); }, "iid", nullptr);
 }
 
-// The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32, scv_adaptive_prefix_i32 and
-// scv_iid_prefix_i32 share, in
+// The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32, scv_adaptive_prefix_i32,
+// scv_shortest_prefix_i32 and scv_iid_prefix_i32 share, in
 // the order the entries have always made them; `what` names the entry in every message.  An entry's own checks keep their places in that
 // order: `early` runs behind the shape check (weighted: the rule), `own` behind the P * R bound (the pointers the entry requires).
 // cells_given: the cell outputs of the entry as its message lists them when the caller passed one, NULL when it passed none.
@@ -1877,6 +1896,41 @@ int scv_adaptive_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* to
                                    order, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(), rg[TSUM].at<int64_t>(), rg[VSUM].at<int64_t>(),
                                    rg[TCS].at<int64_t>(), rg[HIST].at<int64_t>(), rg[PER].at<int64_t>(), rg[CELLS].at<scv_cell>(),
                                    rg[CTOK].at<int64_t>(), rg[CVOTES].at<int32_t>(), err);
+        });
+    });
+}
+
+int scv_shortest_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* m_keep,
+                            const int32_t* truth, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end,
+                            uint64_t seed, int32_t M, int mem_kind, int64_t* tie_class_hits_out, int64_t* voted_token_sum_out,
+                            int64_t* spent_token_sum_out, int64_t* latency_sum_out, int64_t* truth_count_sum_out, int64_t* per_resample_out,
+                            scv_cell* cells_out, int64_t* cell_tokens_out) {
+    return guarded([&]() -> int {
+        const char* cells_given = (cells_out || cell_tokens_out) ? "cells_out / cell_tokens_out" : nullptr;
+        if (int rc = check_lane_call("shortest", ctx, P, B, N, p_offset, order, r_begin, r_end, cells_given, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!n_valid || !m_keep || !tie_class_hits_out) return fail(SCV_ERR_ARG, "shortest: n_valid, m_keep and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !tokens || !truth)) return fail(SCV_ERR_ARG, "shortest: pool, tokens and truth are required");
+                return SCV_OK;
+            })) return rc;
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_shortest(ctx, pool, tokens, n_valid, m_keep, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie_class_hits_out,
+                                   voted_token_sum_out, spent_token_sum_out, latency_sum_out, truth_count_sum_out, per_resample_out, cells_out,
+                                   cell_tokens_out, ctx->d_err);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t), budgets = (size_t)B * sizeof(int32_t);
+        enum { POOL, TOK, TRUTH, NV, MK, CELLS, CTOK, TIE, VSUM, SSUM, LSUM, TCS, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(n_valid, budgets), once_in(m_keep, budgets),
+                       rows_out(cells_out, (size_t)B * sizeof(scv_cell)), rows_out(cell_tokens_out, sums),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(voted_token_sum_out, sums), sums_out(spent_token_sum_out, sums),
+                       sums_out(latency_sum_out, sums), sums_out(truth_count_sum_out, sums),
+                       sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing voted, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {
+            return launch_shortest(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[NV].at<const int32_t>(),
+                                   rg[MK].at<const int32_t>(), rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, order, r_begin, r_end, seed, M,
+                                   rg[TIE].at<int64_t>(), rg[VSUM].at<int64_t>(), rg[SSUM].at<int64_t>(), rg[LSUM].at<int64_t>(),
+                                   rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(), rg[CELLS].at<scv_cell>(), rg[CTOK].at<int64_t>(), err);
         });
     });
 }

@@ -99,10 +99,13 @@ struct ResampleArgs {
     // to N), tokens may be NULL
     // appended for SCV_FLAG_OPEN_DOMAIN (every body): rows are encoded by resample_encode_row_open, min_mode is a code (scvote_resample.hip.h)
     int32_t open_domain;
+    // appended for short-m@k (scv_shortest_prefix_i32, scvote_shortest.hip.h): n_valid holds k_b, tokens are required, token_sum takes the voted tokens
+    const int32_t* m_keep;                               // [B] samples kept of the first k_b
+    unsigned long long* spent_sum; unsigned long long* latency_sum;     // [B] (NULL ok)
 };
 using ResampleFn = void (*)(const ResampleArgs);
 constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3,
-                  kResampleModeAdaptive = 4, kResampleModeIid = 5;
+                  kResampleModeAdaptive = 4, kResampleModeIid = 5, kResampleModeShortest = 6;
 constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
 // LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
 // budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
@@ -110,6 +113,14 @@ constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV
 constexpr long long token_budget_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
     return 64 + 6LL * B + 32 + (long long)B * (N + 1) + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) +
            (shuffled ? 2LL : 1LL) * lanes * ((N + 3) / 4);
+}
+// LDS words of a short-m@k workgroup (scvote_shortest.hip.h, in this order): per-budget sums (4 B int64) | tie classes [B][N + 1] | sorted k_b,
+// m_b and their order (3 x 32) | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] | the rows as byte
+// codes, token ranks and their inverse [np_max][3][N4] | the lanes' counts [N4][lanes] | their rank bitmaps [ceil(N / 32)][lanes] | their
+// Fisher-Yates arrays [N4][lanes] (shuffled order only)
+constexpr long long shortest_lds_words(int N, int B, int lanes, int np_max, bool shuffled) {
+    return 8LL * B + (long long)B * (N + 1) + 96 + 64LL * (lanes / 64) + 2LL * np_max + 3LL * np_max * ((N + 3) / 4) +
+           (long long)lanes * ((N + 3) / 4 + (N + 31) / 32) + (shuffled ? (long long)lanes * ((N + 3) / 4) : 0LL);
 }
 // LDS words of an adaptive-vote workgroup (scvote_adaptive.hip.h, in this order): per-rule sums (3 B int64) | caps [32] | rule masks [2] |
 // tie classes [B][N + 1] | stop lengths [B][N + 1] | need as uint16 [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and

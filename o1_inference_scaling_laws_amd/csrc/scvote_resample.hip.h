@@ -32,8 +32,9 @@
 // The <false> instantiation has three more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h),
 // the weighted vote / best-of-N (mode kResampleModeWeighted, scvote_weighted.hip.h) and the vote over draws with replacement (mode
 // kResampleModeIid, scvote_iid.hip.h); the <true> one the vote over the longest prefix
-// that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h) and the vote that stops by a rule on its own state
-// (mode kResampleModeAdaptive, scvote_adaptive.hip.h).
+// that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h), the vote that stops by a rule on its own state
+// (mode kResampleModeAdaptive, scvote_adaptive.hip.h) and the vote over the m shortest of the first k samples (mode kResampleModeShortest,
+// scvote_shortest.hip.h).
 #pragma once
 
 #include "scvote_kernels.hip.h"
@@ -198,6 +199,7 @@ __device__ __forceinline__ int32_t resample_min_mode(const ResampleArgs& a, int6
 #include "scvote_budget.hip.h"
 #include "scvote_weighted.hip.h"
 #include "scvote_adaptive.hip.h"
+#include "scvote_shortest.hip.h"
 #include "scvote_iid.hip.h"
 
 namespace scv {
@@ -212,6 +214,7 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
     } else {
         if (a.mode == kResampleModeTokenBudget) { token_budget_body(a, smem_wg); return; }      // token budgets: scvote_budget.hip.h
         if (a.mode == kResampleModeAdaptive) { adaptive_body(a, smem_wg); return; }             // stopping rules: scvote_adaptive.hip.h
+        if (a.mode == kResampleModeShortest) { shortest_body(a, smem_wg); return; }             // short-m@k: scvote_shortest.hip.h
     }
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lanes = (int)blockDim.x, nwaves = lanes >> 6;

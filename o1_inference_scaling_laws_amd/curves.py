@@ -72,6 +72,25 @@ def token_budget_records(engine, pool, truth, tokens, token_limits, resamples: i
             for b, t in enumerate(limits)]
 
 
+def shortest_vote_records(engine, pool, truth, tokens, pairs, resamples: int | None = None, seed: int = 0):
+    """pool / tokens int32 [P, Npool] (each problem's samples in cache order), truth int32 [P], ``pairs`` a list of (k, m).  For every pair:
+    the accuracy of short-m@k -- k samples in parallel, the vote over the m that finish first (Engine.shortest_prefix,
+    scv_shortest_prefix_i32) -- in the cache order (``resamples=None``, one draw) or averaged over ``resamples`` random orderings, against the
+    compute it spends and against its latency, as records {'k', 'm', 'accuracy', 'avg_tokens_used' (spent: the kept chains, and every other
+    chain up to the moment the m-th finishes), 'avg_voted_tokens', 'avg_latency' (the m-th shortest chain)}.  At most 32 pairs per call of
+    the engine; longer lists are split."""
+    pairs = [(int(k), int(m)) for k, m in pairs]
+    pool = np.asarray(pool, dtype=np.int32)
+    tokens = np.asarray(tokens, dtype=np.int32)
+    recs = []
+    for i in range(0, len(pairs), 32):
+        part = pairs[i:i + 32]
+        res = engine.shortest_prefix(pool, tokens, truth, [k for k, _ in part], [m for _, m in part], resamples=resamples, seed=seed, M=0)
+        recs += [{"k": k, "m": m, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_spent_tokens(b)),
+                  "avg_voted_tokens": float(res.avg_voted_tokens(b)), "avg_latency": float(res.avg_latency(b))} for b, (k, m) in enumerate(part)]
+    return recs
+
+
 def weighted_majority_records(engine, pool, weights, truth, tokens, token_limits, rule, resamples: int | None = None, seed: int = 0):
     """pool / weights / tokens int32 [P, Npool] (the 2^11-token samples of each problem in cache order, each with an integer weight in
     0 .. WEIGHT_MAX: weighted.quantize_weights), truth int32 [P].  For every token limit T >= 2^11 (the budgets of resampled_budgets,

@@ -23,6 +23,7 @@ from .resample import ResampleResult
 from .token_budget import TokenBudgetResult
 from .weighted import WeightedResult
 from .adaptive import AdaptiveResult, check_rules
+from .shortest import ShortestResult
 from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
 
 CELL_DTYPE = np.dtype(
@@ -138,8 +139,8 @@ class Engine:
 
     def __init__(self, device: int | None = None, timing: bool = False, clamp_to_invalid_bin: bool = False, packed_cells: bool = False, _adopt=None,
                  open_domain: bool = False):
-        """``open_domain=True`` (SCV_FLAG_OPEN_DOMAIN, opt-in): the six pool-ordering calls (resample, expected, token budget, weighted, adaptive,
-        iid) take any int32 as an answer value -- no domain error, no clamp -- and the ``min_mode`` of their pool-order cells is the CODE of the
+        """``open_domain=True`` (SCV_FLAG_OPEN_DOMAIN, opt-in): the pool-ordering calls (resample, expected, token budget, weighted, adaptive,
+        iid, shortest) take any int32 as an answer value -- no domain error, no clamp -- and the ``min_mode`` of their pool-order cells is the CODE of the
         smallest modal value (``decode_min_mode`` gives the value).  The dense calls keep the 1024 bins.
 
         ``packed_cells=True`` (SCV_FLAG_PACKED_CELLS, opt-in): ``aggregate_device`` over cells of up to 127 votes writes 4-byte records --
@@ -467,6 +468,32 @@ class Engine:
                                               _np_ptr(cell_votes)))
         return AdaptiveResult(P, R, tie, tok, votes, tcs, hist, per, cells, cell_tokens, cell_votes)
 
+    def shortest_prefix(self, pool, tokens, truth, n_valid, m_keep, resamples: int | None = None, seed: int = 0, r_begin: int = 0,
+                        p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> ShortestResult:
+        """short-m@k: majority vote over the m_keep[b] shortest (fewest tokens, ties by pool index) of the first n_valid[b] samples of each
+        pool ordering (scv_shortest_prefix_i32; CPU mirror: shortest.py).  pool / tokens int32 [P, N] (numpy, N <= 256), truth [P], n_valid
+        / m_keep int32 [B] (B <= 32, any order).  ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells and
+        their spent tokens); otherwise the orderings r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of
+        ``per_resample`` (None: N + 1, which no hit can exceed; 0: not computed).  Blocking."""
+        pool, _, P, N, r0, r1, M, order = _host_orderings(pool, None, resamples, r_begin, M, want_cells)
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
+        m_keep = np.ascontiguousarray(m_keep, dtype=np.int32)
+        if tokens.shape != pool.shape or truth.shape != (P,) or n_valid.ndim != 1 or m_keep.shape != n_valid.shape:
+            raise ValueError("tokens must match pool, truth must be [P], n_valid and m_keep [B]")
+        B = n_valid.shape[0]
+        R = r1 - r0
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        voted, spent, latency, tcs = (np.zeros((B,), dtype=np.int64) for _ in range(4))
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
+        cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
+        check(self._L.scv_shortest_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(m_keep), _np_ptr(truth), P, B,
+                                              N, p_offset, order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(voted),
+                                              _np_ptr(spent), _np_ptr(latency), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
+        return ShortestResult(P, R, tie, voted, spent, latency, tcs, per, cells, cell_tokens)
+
     # ---- DEVICE mode (torch tensors; asynchronous on torch's current stream) --------------------
 
     def _device_call(self, votes, votes_name, row_shape, truth, tokens, n_valid, counters, cells, cell_tokens, overwrite, want_no_cells=True):
@@ -590,7 +617,7 @@ class Engine:
         return out
 
     def _lane_device(self, pool, B, inputs, r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", None)):
-        """Prologue of the five *_prefix_device methods.  Checks ``pool`` (contiguous CUDA int32 [P, N] on the engine's device) and ``inputs`` --
+        """Prologue of the six *_prefix_device methods.  Checks ``pool`` (contiguous CUDA int32 [P, N] on the engine's device) and ``inputs`` --
         (name, tensor, shape, dtype, optional) with shape "P", "PN", "B" or "BN1" ([B, N + 1]) --, derives the orderings (``r_end`` None: the
         pool's own order, one draw), checks or allocates zeroed tie_class_hits and -- when ``M`` or the buffer is given -- per_resample, and binds
         torch's current stream.  ``labels``: how the messages about inputs / int64 outputs name the dtype, where not ``str(dtype)``.
@@ -704,6 +731,37 @@ class Engine:
                                                   _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(per_resample), _ptr(cells),
                                                   _ptr(cell_tokens)))
         return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
+
+    def shortest_prefix_device(self, pool, tokens, truth, n_valid, m_keep, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
+                               p_offset: int = 0, tie_class_hits=None, voted_token_sum=None, spent_token_sum=None, latency_sum=None,
+                               truth_count_sum=None, per_resample=None, M: int | None = None, cells=None, cell_tokens=None,
+                               want_cells: bool = False):
+        """DEVICE-mode shortest_prefix: pool / tokens torch.int32 cuda [P, N], truth [P], n_valid / m_keep [B].  ``r_end=None``: the pool's own
+        order (r_begin must be 0); otherwise the orderings [r_begin, r_end).  ACCUMULATES into the given int64 buffers (tie_class_hits
+        [B, 1025], voted_token_sum, spent_token_sum, latency_sum, truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left None
+        are allocated zeroed -- per_resample only when ``M`` is given).  Pool order only: OVERWRITES cells (uint8 [P, B, 16]) and cell_tokens
+        (int64 [P, B], the spent tokens), allocated when ``want_cells``.  One launch on torch's current stream, does not synchronise (a
+        negative token count is reported by ``sync``).  Returns (tie_class_hits, voted_token_sum, spent_token_sum, latency_sum,
+        truth_count_sum, per_resample, cells, cell_tokens)."""
+        import torch
+        i32, i64 = torch.int32, torch.int64
+        B = int(n_valid.shape[0])
+        P, N, dev, r_end, order, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("tokens", tokens, "PN", i32, False), ("truth", truth, "P", i32, False), ("n_valid", n_valid, "B", i32, False),
+                      ("m_keep", m_keep, "B", i32, False)), r_begin, r_end, tie_class_hits, per_resample, M)
+        voted_token_sum = _device_tensor(voted_token_sum, (B,), "voted_token_sum", i64, dev, alloc=torch.zeros)
+        spent_token_sum = _device_tensor(spent_token_sum, (B,), "spent_token_sum", i64, dev, alloc=torch.zeros)
+        latency_sum = _device_tensor(latency_sum, (B,), "latency_sum", i64, dev, alloc=torch.zeros)
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", i64, dev, alloc=torch.zeros)
+        if want_cells or cells is not None:
+            cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
+        if want_cells or cell_tokens is not None:
+            cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
+        check(self._L.scv_shortest_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_valid), _ptr(m_keep), _ptr(truth), P, B, N, p_offset,
+                                              order, r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits),
+                                              _ptr(voted_token_sum), _ptr(spent_token_sum), _ptr(latency_sum), _ptr(truth_count_sum),
+                                              _ptr(per_resample), _ptr(cells), _ptr(cell_tokens)))
+        return tie_class_hits, voted_token_sum, spent_token_sum, latency_sum, truth_count_sum, per_resample, cells, cell_tokens
 
     def weighted_prefix_device(self, pool, weights, truth, n_valid, rule: int = _lib.RULE_WEIGHT_SUM, r_begin: int = 0, r_end: int | None = None,
                                seed: int = 0, p_offset: int = 0, tokens=None, tie_class_hits=None, token_sum=None, per_resample=None,
