@@ -559,6 +559,46 @@ int scv_iid_prefix_i32(scv_ctx* ctx,
                        int64_t* truth_count_sum_out, int64_t* per_resample_out);
 
 /*
+ * Resampled majority vote over WIDE pools: the expected maj@k over random orderings of one pool of up to SCV_WIDE_MAX_N = 4096 samples per
+ * problem (new semantics, not in the reference).  scv_resample_prefix_i32 keeps one lane per (problem, ordering) and stops at N = 256; beyond
+ * that only the pool-order curve of scv_aggregate_prefix_i32 was left, which is one draw.  Arguments, outputs and modes are exactly those of
+ * scv_resample_prefix_i32; the ORDERING is not: a Fisher-Yates walk is sequential, so the order is defined by sort keys.
+ *   pool / tokens  int32 [P, N] (tokens may be NULL); n_valid int32 [B] (required, any order, duplicates fine); truth int32 [P]
+ * For problem p (global index pg = p_offset + p) and resample r in [r_begin, r_end):
+ *   s     = mix64((seed ^ 0x8EBC6AF09C88C6E3) + G * (pg + 1))                       (uint64, wrapping; mix64, G as above)
+ *   u_i   = mix64(s + G * ((uint64)r * 4096 + i + 1))                               i = 0 .. N-1
+ *   w_i   = (u_i & ~4095) | i                                                       52 random bits, the pool index below them
+ *   order = the samples sorted ascending by w_i                                     (the w_i are distinct: every sort gives the same order)
+ *   cell (p, r, b) = statistics.multimode over pool[p, order[0 : k_b]],  k_b = clamp(n_valid[b], 0, N)
+ * The stride of 4096 per resample keeps the streams of different r apart, and the salt differs from every other entry's, so this call's
+ * orderings are independent of theirs for the same seed.  The prefixes of one resample are nested across budgets.  Each prefix is a uniformly
+ * random k-subset EXCEPT when two of the 52-bit keys of an ordering tie (the pool index then decides): the probability of any tie in one
+ * ordering is below N^2 / 2^53 (< 2^-29 at N = 4096), far under the resolution of any R a call can draw.
+ * NOT bit-compatible with scv_resample_prefix_i32 at N <= 256: the orderings differ, only the expectation is the same (at k_b = N every
+ * output is the same: the ordering cannot matter there).  At N <= 256 scv_resample_prefix_i32 is the entry to call: one lane per ordering
+ * beats one workgroup per ordering there (csrc/scvote_wide.hip.h).
+ * Votes, truths, the empty prefix, error bit 0 / SCV_ERR_DOMAIN, SCV_FLAG_CLAMP_TO_INVALID_BIN and error bit 1 for a hit with n_modes >= M
+ * are as in scv_resample_prefix_i32.  SCV_FLAG_OPEN_DOMAIN does NOT apply: like the dense entries this one keeps the 1024 bins (it votes
+ * into a 1024-bin histogram), and a vote outside them is a domain error with the flag on or off.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a budget, as in scv_resample_prefix_i32:
+ *   tie_class_hits_out int64 [B, 1025] (required), token_sum_out int64 [B] (NULL ok; requires tokens), truth_count_sum_out int64 [B] (NULL ok),
+ *   per_resample_out int64 [r_end - r_begin, B, M] (NULL ok; a hit with n_modes >= M sets error bit 1)
+ * DEVICE mode ACCUMULATES into every output (+=) and only enqueues: one launch, no allocation, no synchronisation, legal under hipGraph
+ * capture.  HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices of r and shards of p (p_offset) add
+ * up to the whole call bit for bit.  Limits: 1 <= N <= SCV_WIDE_MAX_N, 1 <= B <= 32, 0 <= r_begin <= r_end < 2^31, p_offset >= 0, M >= 1
+ * when per_resample_out is given, token_sum_out only with tokens; anything else is SCV_ERR_ARG with nothing queued.  One workgroup per
+ * (problem, resample): a bitonic sort of the padded words in LDS, then one 1024-bin histogram walked budget by budget.
+ */
+#define SCV_WIDE_MAX_N 4096
+int scv_resample_wide_i32(scv_ctx* ctx,
+                          const int32_t* pool, const int32_t* tokens,
+                          const int32_t* n_valid, const int32_t* truth,
+                          int64_t P, int32_t B, int64_t N, int64_t p_offset,
+                          int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                          int64_t* tie_class_hits_out, int64_t* token_sum_out,
+                          int64_t* truth_count_sum_out, int64_t* per_resample_out);
+
+/*
  * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
  * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
  * seed and nothing left to converge.

@@ -1468,19 +1468,54 @@ int launch_iid(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const i
                             [&](int lanes, int np) { return scv::iid_lds_words((int)N, B, lanes, np); }, "iid", nullptr);
 }
 
+// scv_resample_wide_i32 on device pointers: one launch of the wide body of scv_resample_prefix<false> (scvote_wide.hip.h), accumulating into the
+// outputs.  One workgroup per (problem, resample) item, its size and its LDS from N (wide_lanes, wide_lds_words: 51 KiB at N = 4096 with 13
+// budgets, 61 KiB with 32 -- every N in range fits one workgroup); a persistent grid of as many workgroups as stay resident, each with a
+// contiguous run of items.  Not through launch_lane_body: no lanes to choose, no rows per chunk.
+int launch_wide(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
+                int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    scv::ResampleArgs a = lane_args(pool, tokens, n_valid, truth, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, seed, M, tie, tok_sum,
+                                    truth_sum, per_resample, err);
+    a.mode = scv::kResampleModeWide;
+    const scv::ResampleFn fn = pick_resample_kernel(false);
+    const int lanes = scv::wide_lanes((int)N);
+    const size_t lds = (size_t)scv::wide_lds_words((int)N, B) * sizeof(uint32_t);
+    if ((int64_t)lds > ctx->lds_max) return fail(SCV_ERR_ARG, "resample_wide: N=%d B=%d does not fit the LDS of one workgroup", a.N, a.B);
+    SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+    int per_cu = 0;
+    SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds));
+    if (per_cu < 1) per_cu = 1;
+    const int64_t items = P * a.R;
+    int64_t grid = (int64_t)ctx->num_cus * per_cu;
+    if (grid > items) grid = items;
+    if (ctx->grid_override > 0) grid = ctx->grid_override;
+    EventPair* ev = nullptr;
+    if (int rc = next_event_pair(ctx, &ev)) return rc;
+    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)lanes), lds, ctx->stream, a);
+    SCV_HIP(hipGetLastError());
+    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
+    ctx->err_dirty = true;
+    return SCV_OK;
+}
+
 // The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32, scv_adaptive_prefix_i32,
 // scv_shortest_prefix_i32 and scv_iid_prefix_i32 share, in
 // the order the entries have always made them; `what` names the entry in every message.  An entry's own checks keep their places in that
 // order: `early` runs behind the shape check (weighted: the rule), `own` behind the P * R bound (the pointers the entry requires).
 // cells_given: the cell outputs of the entry as its message lists them when the caller passed one, NULL when it passed none.
-// scv_resample_prefix_i32 has neither an order nor cells: it passes SCV_ORDER_SHUFFLED and NULL.
+// scv_resample_prefix_i32 has neither an order nor cells: it passes SCV_ORDER_SHUFFLED and NULL.  n_max: the largest pool of the entry (the lane
+// bodies: kResampleMaxN; scv_resample_wide_i32, which shares the checks and the staging but not the lane layout: SCV_WIDE_MAX_N).
 template <class Early, class Own>
 int check_lane_call(const char* what, const scv_ctx* ctx, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin,
-                    int32_t r_end, const char* cells_given, bool per_resample, int32_t M, int mem_kind, Early early, Own own) {
+                    int32_t r_end, const char* cells_given, bool per_resample, int32_t M, int mem_kind, Early early, Own own,
+                    int n_max = scv::kResampleMaxN) {
     if (!ctx) return fail(SCV_ERR_ARG, "ctx is NULL");
-    if (N < 1 || N > scv::kResampleMaxN || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
+    if (N < 1 || N > n_max || B < 1 || B > scv::kResampleMaxB || P < 0 || P > (1ll << 40) || p_offset < 0 || r_begin < 0 || r_end < r_begin)
         return fail(SCV_ERR_ARG, "%s: bad shape P=%lld B=%d N=%lld p_offset=%lld r=[%d,%d) (1 <= N <= %d, 1 <= B <= %d, 0 <= r_begin <= r_end)",
-                    what, (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, scv::kResampleMaxN, scv::kResampleMaxB);
+                    what, (long long)P, B, (long long)N, (long long)p_offset, r_begin, r_end, n_max, scv::kResampleMaxB);
     if (int rc = early()) return rc;
     if (order != SCV_ORDER_POOL && order != SCV_ORDER_SHUFFLED) return fail(SCV_ERR_ARG, "%s: bad order %d", what, order);
     if (order == SCV_ORDER_POOL && (r_begin != 0 || r_end != 1))
@@ -1964,6 +1999,36 @@ int scv_iid_prefix_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens,
             return launch_iid(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[ND].at<const int32_t>(),
                               rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
                               rg[TSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(), err);
+        });
+    });
+}
+
+int scv_resample_wide_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
+                          int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
+                          int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* truth_count_sum_out,
+                          int64_t* per_resample_out) {
+    return guarded([&]() -> int {
+        if (int rc = check_lane_call("resample_wide", ctx, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, nullptr, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!n_valid || !tie_class_hits_out) return fail(SCV_ERR_ARG, "resample_wide: n_valid and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !truth)) return fail(SCV_ERR_ARG, "resample_wide: pool and truth are required");
+                if (token_sum_out && !tokens) return fail(SCV_ERR_ARG, "resample_wide: token_sum_out needs tokens");
+                return SCV_OK;
+            }, SCV_WIDE_MAX_N)) return rc;
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_wide(ctx, pool, tokens, n_valid, truth, P, B, N, p_offset, r_begin, r_end, seed, M, tie_class_hits_out, token_sum_out,
+                               truth_count_sum_out, per_resample_out, ctx->d_err);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t);
+        enum { POOL, TOK, TRUTH, NV, TIE, TSUM, TCS, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(n_valid, (size_t)B * sizeof(int32_t)),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums), sums_out(truth_count_sum_out, sums),
+                       sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing drawn, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {     // (sums add: chunks of problems)
+            return launch_wide(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[NV].at<const int32_t>(),
+                               rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
+                               rg[TSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(), err);
         });
     });
 }

@@ -105,7 +105,7 @@ struct ResampleArgs {
 };
 using ResampleFn = void (*)(const ResampleArgs);
 constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3,
-                  kResampleModeAdaptive = 4, kResampleModeIid = 5, kResampleModeShortest = 6;
+                  kResampleModeAdaptive = 4, kResampleModeIid = 5, kResampleModeShortest = 6, kResampleModeWide = 7;
 constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
 // LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
 // budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
@@ -160,6 +160,18 @@ constexpr int kResampleMaxN = 256, kResampleMaxB = 32, kResampleMaxLanes = 256;
 // the rows as byte codes [np_max][N4] | the lanes' Fisher-Yates arrays [N4][lanes] | their counts [N4][lanes]
 constexpr long long resample_lds_words(int N, int B, int lanes, int np_max) {
     return 4LL * B + (long long)B * (N + 1) + 64 + 64LL * (lanes / 64) + 2LL * np_max + (long long)np_max * ((N + 3) / 4) + 2LL * lanes * ((N + 3) / 4);
+}
+// The wide body (scv_resample_wide_i32, scvote_wide.hip.h; mode kResampleModeWide of the <false> instantiation): one workgroup per (problem,
+// resample), 1 <= N <= SCV_WIDE_MAX_N.  The sort runs over wide_pad(N) words (the next power of two, at least 2); the workgroup has one lane per
+// compare-exchange of a stage, 64 .. 256; the LDS tie table has wide_tie_cols(N) columns, larger classes go to global memory one by one.
+constexpr int wide_pad(int N) { int n2 = 2; while (n2 < N) n2 <<= 1; return n2; }
+constexpr int wide_lanes(int N) { const int h = wide_pad(N) / 2; return h < 64 ? 64 : (h > kResampleMaxLanes ? kResampleMaxLanes : h); }
+constexpr int wide_tie_cols(int N) { return (N < 127 ? N : 127) + 1; }
+// LDS words of a wide workgroup (the kernel's layout, in this order): the sort words (wide_pad(N) uint64) | per-budget sums (2 B int64) | the
+// waves' token sums (2 x 4 int64) | the histogram [1024] | tie classes [B][wide_tie_cols(N)] | the waves' (max, modes) (2 x 4 x 2) | sorted
+// budgets and their order (2 x 32) | the row as 16-bit bins [N]
+constexpr long long wide_lds_words(int N, int B) {
+    return 2LL * wide_pad(N) + 4LL * B + 16 + kBins + (long long)B * wide_tie_cols(N) + 16 + 64 + (N + 1) / 2;
 }
 ResampleFn pick_resample_kernel(bool tok);
 

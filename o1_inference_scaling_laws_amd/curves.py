@@ -4,6 +4,7 @@ scv_resample_prefix_i32).
 The reference's majority-vote tail (o1.py:266-277: T >= 2^11 votes over the first N = T // 2^11 samples of the 2^11-token pool)
 is one ordering of the cache.  ``expected_majority_records`` averages each point over ``resamples`` random orderings of the same
 pool and returns it in the reference's log schema, so plot_helpers can draw the smoothed tail next to the single-ordering one.
+``wide_majority_records`` is the same average for pools of up to 4096 samples (Engine.resample_wide).
 ``exact_majority_records`` gives the limit of that average -- the mean over all k-subsets -- with no seed and no resample count.
 ``token_budget_records`` ends each vote where a budget of TOKENS runs out instead of after a number of samples;
 ``adaptive_vote_records`` where a stopping rule on the vote's own state says it is settled.  ``iid_majority_records`` draws WITH
@@ -41,6 +42,21 @@ def expected_majority_records(engine, pool, truth, tokens, token_limits, resampl
     if len(ns) and ns.max() > pool.shape[1]:
         raise ValueError(f"token limit {budgets[int(ns.argmax())][0]} needs {int(ns.max())} samples per problem; the pool has {pool.shape[1]}")
     res = engine.resample_prefix(pool, truth, ns, resamples, seed, tokens=tokens, M=0)
+    return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
+            for b, (t, _n) in enumerate(budgets)]
+
+
+def wide_majority_records(engine, pool, truth, tokens, token_limits, resamples: int, seed: int):
+    """As expected_majority_records for pools of up to 4096 samples per problem (Engine.resample_wide, scv_resample_wide_i32): the same
+    records {'token_limit', 'accuracy', 'avg_tokens_used'} (o1.py:278-283) for T >= 2^11, N = T // 2^11 <= Npool.  The orderings are drawn by
+    sort keys, not by the shuffle of expected_majority_records: the two curves agree in expectation, not draw by draw.  ``tokens`` may be None
+    (avg_tokens_used is then 0.0)."""
+    budgets = resampled_budgets(token_limits)
+    pool = np.asarray(pool, dtype=np.int32)
+    ns = np.array([n for _t, n in budgets], dtype=np.int32)
+    if len(ns) and ns.max() > pool.shape[1]:
+        raise ValueError(f"token limit {budgets[int(ns.argmax())][0]} needs {int(ns.max())} samples per problem; the pool has {pool.shape[1]}")
+    res = engine.resample_wide(pool, truth, ns, resamples, seed, tokens=tokens, M=0)
     return [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b))}
             for b, (t, _n) in enumerate(budgets)]
 

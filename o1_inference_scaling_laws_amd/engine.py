@@ -332,6 +332,31 @@ class Engine:
                                               _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
         return ResampleResult(P, R, tie, tok, tcs, per)
 
+    def resample_wide(self, pool, truth, n_valid, resamples: int, seed: int, tokens=None, r_begin: int = 0, p_offset: int = 0,
+                      M: int | None = None) -> ResampleResult:
+        """Expected majority vote over ``resamples`` random orderings of each pool of up to WIDE_MAX_N = 4096 samples
+        (scv_resample_wide_i32; CPU mirror: wide.py).  The signature and the result of ``resample_prefix``; the orderings are defined by sort
+        keys and are NOT those of ``resample_prefix`` -- only the expectation is shared.  At N <= 256 ``resample_prefix`` is the one to call.
+        pool int32 [P, N] (numpy), n_valid int32 [B] (B <= 32).  ``M``: classes of ``per_resample`` (None: max budget + 1, which no hit can
+        exceed; 0: per_resample is not computed).  Blocking."""
+        pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
+        if truth.shape != (P,) or n_valid.ndim != 1:
+            raise ValueError("truth must be [P] and n_valid [B]")
+        B = n_valid.shape[0]
+        R = r1 - r0
+        if M is None:
+            M = int(np.clip(n_valid, 0, N).max(initial=0)) + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64)
+        tcs = np.zeros((B,), dtype=np.int64)
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        check(self._L.scv_resample_wide_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth), P, B, N, p_offset,
+                                            r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
+                                            _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
+        return ResampleResult(P, R, tie, tok, tcs, per)
+
     def iid_prefix(self, pool, truth, n_draws, resamples: int, seed: int, tokens=None, r_begin: int = 0, p_offset: int = 0,
                    M: int | None = None) -> ResampleResult:
         """Majority vote over draws WITH replacement from each pool, past its size: the plug-in estimate of maj@k (scv_iid_prefix_i32;
@@ -660,6 +685,25 @@ class Engine:
         check(self._L.scv_resample_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_valid), _ptr(truth), P, B, N, p_offset, r_begin, r_end,
                                               seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum),
                                               _ptr(truth_count_sum), _ptr(per_resample)))
+        return tie_class_hits, token_sum, truth_count_sum, per_resample
+
+    def resample_wide_device(self, pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
+                             tie_class_hits=None, token_sum=None, truth_count_sum=None, per_resample=None, M: int | None = None):
+        """DEVICE-mode resample_wide: pool / tokens torch.int32 cuda [P, N] (N <= 4096), n_valid [B], truth [P].  ACCUMULATES into the given
+        int64 buffers (tie_class_hits [B, 1025], token_sum [B], truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left None
+        are allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise (a hit with
+        n_modes >= M is reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
+        import torch
+        i32 = torch.int32
+        B = int(n_valid.shape[0])
+        P, N, dev, _, _, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("truth", truth, "P", i32, True), ("tokens", tokens, "PN", i32, True), ("n_valid", n_valid, "B", i32, True)),
+            r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", "int64"))
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", torch.int64, dev, "int64", torch.zeros) if tokens is not None else None
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", torch.int64, dev, "int64", torch.zeros)
+        check(self._L.scv_resample_wide_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_valid), _ptr(truth), P, B, N, p_offset, r_begin, r_end,
+                                            seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum),
+                                            _ptr(truth_count_sum), _ptr(per_resample)))
         return tie_class_hits, token_sum, truth_count_sum, per_resample
 
     def iid_prefix_device(self, pool, truth, n_draws, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
