@@ -58,7 +58,8 @@ extern "C" {
                                       o1_inference_scaling_laws_amd/engine.py unpack_cells */
 
 #define SCV_FLAG_OPEN_DOMAIN 0x8u /* OPT-IN: the pool-ordering entries (scv_resample_prefix_i32, scv_expected_majority_i32, scv_token_budget_prefix_i32,
-                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32, and scv_shortest_prefix_i32, which reaches
+                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32, scv_resample_wide_i32 -- rows of up to 4096
+                                      values, see there for tie classes beyond the table --, and scv_shortest_prefix_i32, which reaches
                                       the same row encoder and whose cells_out[..].min_mode is then the CODE) take ANY int32 as an answer value: negative
                                       numbers, large integers, 32-bit hashes of normalised answer strings.  Two votes are the same value only when
                                       the integers are equal.  A vote's code is the rank of its value among the distinct values of the whole row
@@ -578,8 +579,16 @@ int scv_iid_prefix_i32(scv_ctx* ctx,
  * output is the same: the ordering cannot matter there).  At N <= 256 scv_resample_prefix_i32 is the entry to call: one lane per ordering
  * beats one workgroup per ordering there (csrc/scvote_wide.hip.h).
  * Votes, truths, the empty prefix, error bit 0 / SCV_ERR_DOMAIN, SCV_FLAG_CLAMP_TO_INVALID_BIN and error bit 1 for a hit with n_modes >= M
- * are as in scv_resample_prefix_i32.  SCV_FLAG_OPEN_DOMAIN does NOT apply: like the dense entries this one keeps the 1024 bins (it votes
- * into a 1024-bin histogram), and a vote outside them is a domain error with the flag on or off.
+ * are as in scv_resample_prefix_i32.
+ * Under SCV_FLAG_OPEN_DOMAIN every int32 is a value of its own, exactly as the flag is defined for the other pool-ordering entries: a vote's
+ * code is the rank of its value among the D distinct values of the whole row pool[p, 0:N] in ascending signed order, 1 <= D <= N -- there is
+ * no limit of 1024 --, the truth hits when it equals a modal value, whatever its magnitude, and a truth absent from the row never hits.  No
+ * domain error (never error bit 0) and SCV_FLAG_CLAMP_TO_INVALID_BIN has no effect.  Orderings, key streams, the salt, token sums, slices of
+ * r, shards of p, the HOST / DEVICE rules, graph capture, the argument list and the limits are unchanged, and a flag-on call on a pool inside
+ * 0..1023 gives the same bits in every output as the flag-off call (the relabelling preserves equality).  tie_class_hits_out stays [B, 1025]:
+ * with D > 1024 a hit can have n_modes >= 1025, which has no column -- such a hit is counted in NEITHER table and sets error bit 1 (the rule
+ * for n_modes >= M, applied to the main table): SCV_ERR_ARG at the call in HOST mode, at scv_sync in DEVICE mode, nothing dropped silently;
+ * truth_count_sum_out and token_sum_out of that cell are still added.  A budget of at most 1024 samples can never reach it.
  * Outputs, summed over the P x (r_end - r_begin) cells of a budget, as in scv_resample_prefix_i32:
  *   tie_class_hits_out int64 [B, 1025] (required), token_sum_out int64 [B] (NULL ok; requires tokens), truth_count_sum_out int64 [B] (NULL ok),
  *   per_resample_out int64 [r_end - r_begin, B, M] (NULL ok; a hit with n_modes >= M sets error bit 1)
@@ -587,7 +596,8 @@ int scv_iid_prefix_i32(scv_ctx* ctx,
  * capture.  HOST mode overwrites, stages chunks of problems through device memory and blocks.  Slices of r and shards of p (p_offset) add
  * up to the whole call bit for bit.  Limits: 1 <= N <= SCV_WIDE_MAX_N, 1 <= B <= 32, 0 <= r_begin <= r_end < 2^31, p_offset >= 0, M >= 1
  * when per_resample_out is given, token_sum_out only with tokens; anything else is SCV_ERR_ARG with nothing queued.  One workgroup per
- * (problem, resample): a bitonic sort of the padded words in LDS, then one 1024-bin histogram walked budget by budget.
+ * (problem, resample): a bitonic sort of the padded words in LDS, then one 1024-bin histogram walked budget by budget (open domain: one
+ * more sort per problem of a workgroup's run encodes the row, and the histogram has the row's D bins).
  */
 #define SCV_WIDE_MAX_N 4096
 int scv_resample_wide_i32(scv_ctx* ctx,

@@ -822,7 +822,7 @@ int check_err_word(scv_ctx* ctx, uint32_t w) {
     }
     if ((w & 1u) && !(ctx->flags & SCV_FLAG_CLAMP_TO_INVALID_BIN))
         return fail(SCV_ERR_DOMAIN, "a vote outside bins 0..1023 was seen; results are invalid");
-    if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap / resample: a hit had n_modes >= M");
+    if (w & 2u) return fail(SCV_ERR_ARG, "bootstrap / resample: a hit had n_modes >= M (resample_wide, open domain: or >= SCV_TIE_CLASSES)");
     if (w & 16u) return fail(SCV_ERR_ARG, "token_budget / shortest: a token count was negative; results are invalid");
     if (w & 32u) return fail(SCV_ERR_ARG, "weighted: a weight was outside 0..%d; results are invalid", SCV_WEIGHT_MAX);
     if (w & 64u) return fail(SCV_ERR_ARG, "adaptive: a rule flag had a bit other than SCV_STOP_DECIDED; results are invalid");
@@ -1471,7 +1471,8 @@ int launch_iid(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const i
 // scv_resample_wide_i32 on device pointers: one launch of the wide body of scv_resample_prefix<false> (scvote_wide.hip.h), accumulating into the
 // outputs.  One workgroup per (problem, resample) item, its size and its LDS from N (wide_lanes, wide_lds_words: 51 KiB at N = 4096 with 13
 // budgets, 61 KiB with 32 -- every N in range fits one workgroup); a persistent grid of as many workgroups as stay resident, each with a
-// contiguous run of items.  Not through launch_lane_body: no lanes to choose, no rows per chunk.
+// contiguous run of items.  Not through launch_lane_body: no lanes to choose, no rows per chunk.  On a SCV_FLAG_OPEN_DOMAIN context the body
+// encodes its rows by value and its histogram holds max(1024, N) 16-bit counts (55 KiB at N = 4096 with 13 budgets, 65 KiB with 32).
 int launch_wide(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
                 int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
                 int64_t* tie, int64_t* tok_sum, int64_t* truth_sum, int64_t* per_resample, uint32_t* err) {
@@ -1479,9 +1480,10 @@ int launch_wide(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const 
     scv::ResampleArgs a = lane_args(pool, tokens, n_valid, truth, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, seed, M, tie, tok_sum,
                                     truth_sum, per_resample, err);
     a.mode = scv::kResampleModeWide;
+    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;        // (its own launch: not through launch_lane_body)
     const scv::ResampleFn fn = pick_resample_kernel(false);
     const int lanes = scv::wide_lanes((int)N);
-    const size_t lds = (size_t)scv::wide_lds_words((int)N, B) * sizeof(uint32_t);
+    const size_t lds = (size_t)scv::wide_lds_words((int)N, B, a.open_domain != 0) * sizeof(uint32_t);
     if ((int64_t)lds > ctx->lds_max) return fail(SCV_ERR_ARG, "resample_wide: N=%d B=%d does not fit the LDS of one workgroup", a.N, a.B);
     SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
     int per_cu = 0;

@@ -168,10 +168,13 @@ constexpr int wide_pad(int N) { int n2 = 2; while (n2 < N) n2 <<= 1; return n2; 
 constexpr int wide_lanes(int N) { const int h = wide_pad(N) / 2; return h < 64 ? 64 : (h > kResampleMaxLanes ? kResampleMaxLanes : h); }
 constexpr int wide_tie_cols(int N) { return (N < 127 ? N : 127) + 1; }
 // LDS words of a wide workgroup (the kernel's layout, in this order): the sort words (wide_pad(N) uint64) | per-budget sums (2 B int64) | the
-// waves' token sums (2 x 4 int64) | the histogram [1024] | tie classes [B][wide_tie_cols(N)] | the waves' (max, modes) (2 x 4 x 2) | sorted
-// budgets and their order (2 x 32) | the row as 16-bit bins [N]
-constexpr long long wide_lds_words(int N, int B) {
-    return 2LL * wide_pad(N) + 4LL * B + 16 + kBins + (long long)B * wide_tie_cols(N) + 16 + 64 + (N + 1) / 2;
+// waves' token sums (2 x 4 int64) | the histogram (wide_hist_words) | tie classes [B][wide_tie_cols(N)] | the waves' (max, modes) (2 x 4 x 2) |
+// sorted budgets and their order (2 x 32) | the row as 16-bit bins [N]
+// The histogram: 1024 words, one per bin; under SCV_FLAG_OPEN_DOMAIN max(1024, N) 16-bit counts, two per word (a row has at most N distinct
+// values and a count is at most N <= 4096).
+constexpr long long wide_hist_words(int N, bool open) { return open ? ((N > kBins ? N : kBins) + 1) / 2 : kBins; }
+constexpr long long wide_lds_words(int N, int B, bool open) {
+    return 2LL * wide_pad(N) + 4LL * B + 16 + wide_hist_words(N, open) + (long long)B * wide_tie_cols(N) + 16 + 64 + (N + 1) / 2;
 }
 ResampleFn pick_resample_kernel(bool tok);
 

@@ -50,7 +50,8 @@ def wide_majority_records(engine, pool, truth, tokens, token_limits, resamples: 
     """As expected_majority_records for pools of up to 4096 samples per problem (Engine.resample_wide, scv_resample_wide_i32): the same
     records {'token_limit', 'accuracy', 'avg_tokens_used'} (o1.py:278-283) for T >= 2^11, N = T // 2^11 <= Npool.  The orderings are drawn by
     sort keys, not by the shuffle of expected_majority_records: the two curves agree in expectation, not draw by draw.  ``tokens`` may be None
-    (avg_tokens_used is then 0.0)."""
+    (avg_tokens_used is then 0.0).  With an ``Engine(open_domain=True)`` the pool may hold any int32 (scv_resample_wide_i32 under
+    SCV_FLAG_OPEN_DOMAIN)."""
     budgets = resampled_budgets(token_limits)
     pool = np.asarray(pool, dtype=np.int32)
     ns = np.array([n for _t, n in budgets], dtype=np.int32)

@@ -140,7 +140,7 @@ class Engine:
     def __init__(self, device: int | None = None, timing: bool = False, clamp_to_invalid_bin: bool = False, packed_cells: bool = False, _adopt=None,
                  open_domain: bool = False):
         """``open_domain=True`` (SCV_FLAG_OPEN_DOMAIN, opt-in): the pool-ordering calls (resample, expected, token budget, weighted, adaptive,
-        iid, shortest) take any int32 as an answer value -- no domain error, no clamp -- and the ``min_mode`` of their pool-order cells is the CODE of the
+        iid, shortest, resample_wide) take any int32 as an answer value -- no domain error, no clamp -- and the ``min_mode`` of their pool-order cells is the CODE of the
         smallest modal value (``decode_min_mode`` gives the value).  The dense calls keep the 1024 bins.
 
         ``packed_cells=True`` (SCV_FLAG_PACKED_CELLS, opt-in): ``aggregate_device`` over cells of up to 127 votes writes 4-byte records --
@@ -338,7 +338,9 @@ class Engine:
         (scv_resample_wide_i32; CPU mirror: wide.py).  The signature and the result of ``resample_prefix``; the orderings are defined by sort
         keys and are NOT those of ``resample_prefix`` -- only the expectation is shared.  At N <= 256 ``resample_prefix`` is the one to call.
         pool int32 [P, N] (numpy), n_valid int32 [B] (B <= 32).  ``M``: classes of ``per_resample`` (None: max budget + 1, which no hit can
-        exceed; 0: per_resample is not computed).  Blocking."""
+        exceed; 0: per_resample is not computed).  Blocking.  On an ``Engine(open_domain=True)`` every int32 is a value of its own (up to N
+        distinct values per row, no domain error); a hit that ties 1025 or more ways has no column in ``tie_class_hits`` and raises
+        ScvError (ERR_ARG)."""
         pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
         truth = np.ascontiguousarray(truth, dtype=np.int32)
         n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
@@ -692,7 +694,8 @@ class Engine:
         """DEVICE-mode resample_wide: pool / tokens torch.int32 cuda [P, N] (N <= 4096), n_valid [B], truth [P].  ACCUMULATES into the given
         int64 buffers (tie_class_hits [B, 1025], token_sum [B], truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left None
         are allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise (a hit with
-        n_modes >= M is reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
+        n_modes >= M -- on an ``Engine(open_domain=True)``, where every int32 is a value of its own, also one with n_modes >= 1025 -- is
+        reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
         import torch
         i32 = torch.int32
         B = int(n_valid.shape[0])

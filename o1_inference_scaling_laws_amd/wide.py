@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, NUM_BINS, TIE_CLASSES, ResampleResult
+from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, NUM_BINS, TIE_CLASSES, ResampleResult, dense_codes, truth_codes
 from .synth import G, mix64
 
 SEED_SALT = np.uint64(0x8EBC6AF09C88C6E3)
@@ -37,10 +37,13 @@ def orderings(seed: int, pg: int, r, N: int) -> np.ndarray:
 
 
 def resample_wide(pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
-                  M: int | None = None) -> ResampleResult:
+                  M: int | None = None, open_domain: bool = False) -> ResampleResult:
     """pool int32 [P, N] (1 <= N <= 4096), truth int32 [P], n_valid int32 [B] (budget b votes over the first clamp(n_valid[b], 0, N)
     samples of each ordering), resamples [r_begin, r_end).  ``M``: per_resample classes (None: not computed).  Votes outside 0..1023 count
-    in bin 1023 and set error bit 0; a truth outside the bins never hits."""
+    in bin 1023 and set error bit 0; a truth outside the bins never hits.
+    ``open_domain`` (SCV_FLAG_OPEN_DOMAIN): every int32 is a value of its own -- a vote's bin is the rank of its value among the D <= N
+    distinct values of its row, the truth hits when it equals a modal value, never error bit 0.  A hit with n_modes >= 1025 (D > 1024 only)
+    has no column in tie_class_hits: it sets error bit 1 and is counted in neither table; its truth count and tokens are still added."""
     pool = np.asarray(pool)
     if pool.ndim != 2:
         raise ValueError("pool must be [P, N]")
@@ -58,10 +61,18 @@ def resample_wide(pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tok
     tsum = np.zeros(B, dtype=np.int64)
     tcsum = np.zeros(B, dtype=np.int64)
     per = np.zeros((R, B, M), dtype=np.int64) if M is not None else None
-    v = pool.astype(np.int64)
-    bad = (v < 0) | (v >= NUM_BINS)
-    bins = np.where(bad, NUM_BINS - 1, v)
-    err = ERR_DOMAIN_BIT if bad.any() else 0
+    if open_domain:
+        bins, uniq, _ = dense_codes(pool, True)
+        tbin = truth_codes(uniq, truth, True)                            # the truth's bin, or -1
+        nbins = [len(u) for u in uniq]
+        err = 0
+    else:
+        v = pool.astype(np.int64)
+        bad = (v < 0) | (v >= NUM_BINS)
+        bins = np.where(bad, NUM_BINS - 1, v)
+        tbin = np.where((truth >= 0) & (truth < NUM_BINS), truth, -1)
+        nbins = [NUM_BINS] * P
+        err = ERR_DOMAIN_BIT if bad.any() else 0
     if P * R == 0:
         return ResampleResult(P, R, tie, tsum, tcsum, per, err)
     tok_rows = None if tokens is None else np.asarray(tokens, dtype=np.int64)
@@ -73,21 +84,24 @@ def resample_wide(pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tok
         order = orderings(seed, p_offset + p, rs, N)[:, :kmax]
         votes = bins[p][order]                                       # [R, kmax] in drawing order
         tok_cum = None if tok_rows is None else np.cumsum(tok_rows[p][order], axis=1)
-        t = int(truth[p])
-        cnt = np.zeros((R, NUM_BINS), dtype=np.int64)
+        t, D = int(tbin[p]), nbins[p]
+        cnt = np.zeros((R, D), dtype=np.int64)
         at = 0
         for b in by_k:
             k = int(ks[b])
             if k == 0:                                               # the empty prefix: no hit, nothing to add
                 continue
             if k > at:
-                cnt += np.bincount((lane[:, None] * NUM_BINS + votes[:, at:k]).reshape(-1), minlength=R * NUM_BINS).reshape(R, NUM_BINS)
+                cnt += np.bincount((lane[:, None] * D + votes[:, at:k]).reshape(-1), minlength=R * D).reshape(R, D)
                 at = k
             maxc = cnt.max(axis=1)
             nmodes = (cnt == maxc[:, None]).sum(axis=1)
-            tc = cnt[:, t] if 0 <= t < NUM_BINS else np.zeros(R, dtype=np.int64)
-            hit = (tc == maxc) if 0 <= t < NUM_BINS else np.zeros(R, dtype=bool)
-            tie[b] += np.bincount(nmodes[hit], minlength=TIE_CLASSES)[:TIE_CLASSES]
+            tc = cnt[:, t] if t >= 0 else np.zeros(R, dtype=np.int64)
+            hit = (tc == maxc) if t >= 0 else np.zeros(R, dtype=bool)
+            if (nmodes[hit] >= TIE_CLASSES).any():                        # (open domain, D > 1024) no column for the class: counted nowhere
+                err |= ERR_CLASS_BIT
+                hit = hit & (nmodes < TIE_CLASSES)
+            tie[b] += np.bincount(nmodes[hit], minlength=TIE_CLASSES)
             tcsum[b] += int(tc.sum())
             if tok_cum is not None:
                 tsum[b] += int(tok_cum[:, k - 1].sum())
