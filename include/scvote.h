@@ -58,7 +58,7 @@ extern "C" {
                                       o1_inference_scaling_laws_amd/engine.py unpack_cells */
 
 #define SCV_FLAG_OPEN_DOMAIN 0x8u /* OPT-IN: the pool-ordering entries (scv_resample_prefix_i32, scv_expected_majority_i32, scv_token_budget_prefix_i32,
-                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32, scv_resample_wide_i32 -- rows of up to 4096
+                                      scv_weighted_prefix_i32, scv_adaptive_prefix_i32, scv_iid_prefix_i32, scv_resample_wide_i32 and scv_token_budget_wide_i32 -- rows of up to 4096
                                       values, see there for tie classes beyond the table --, and scv_shortest_prefix_i32, which reaches
                                       the same row encoder and whose cells_out[..].min_mode is then the CODE) take ANY int32 as an answer value: negative
                                       numbers, large integers, 32-bit hashes of normalised answer strings.  Two votes are the same value only when
@@ -609,6 +609,56 @@ int scv_resample_wide_i32(scv_ctx* ctx,
                           int64_t* truth_count_sum_out, int64_t* per_resample_out);
 
 /*
+ * Token-budget majority vote over WIDE pools: the vote over the longest prefix of an ordering of one pool of up to SCV_WIDE_MAX_N = 4096
+ * samples per problem that fits a budget of TOKENS (new semantics, not in the reference).  scv_token_budget_prefix_i32 stops at N = 256 and
+ * scv_resample_wide_i32 buys k samples whatever they cost; this entry has the argument list of the first and the orderings of the second.
+ *   pool / tokens  int32 [P, N] (both required; a negative token count is an error); token_budget int64 [B] (required, any order,
+ *   duplicates fine); truth int32 [P]
+ * For problem p (global index pg = p_offset + p), an ordering pi and budget T_b:
+ *   n_b    = max { n <= N : sum_{i<n} tokens[p, pi(i)] <= T_b }   voting stops at the first sample that does not fit (later, cheaper
+ *            samples are not skipped to); samples of 0 tokens always fit; a negative T_b gives the empty prefix; T_b is any int64 and every
+ *            comparison is 64-bit (a running sum of a row is below 4096 * 2^31 = 2^43)
+ *   cell (p, pi, b) = statistics.multimode over pool[p, pi(0 : n_b)], scored as everywhere (1 / n_modes on a hit); its tokens are
+ *            sum_{i<n_b} tokens[p, pi(i)] <= T_b; an empty prefix has no hit and adds 0 to every output
+ *   order  SCV_ORDER_POOL (0): pi is the identity, the cache order (one draw): r_begin = 0, r_end = 1 required
+ *          SCV_ORDER_SHUFFLED (1): pi is EXACTLY the ordering of scv_resample_wide_i32 for (seed, pg, r), r in [r_begin, r_end): the same
+ *          salt, the same stride of 4096 per resample, the same sort words w_i -- NOT the Fisher-Yates orderings of
+ *          scv_token_budget_prefix_i32, with which only the expectation is shared.  In SCV_ORDER_POOL the two entries agree in every output
+ *          at N <= 256.
+ * Votes, truths, error bit 0 / SCV_ERR_DOMAIN, SCV_FLAG_CLAMP_TO_INVALID_BIN and SCV_FLAG_OPEN_DOMAIN are as in scv_resample_wide_i32.  Under
+ * SCV_FLAG_OPEN_DOMAIN D is the number of distinct values of the problem's row; with D > 1024 a hit can tie in 1025 or more ways, and such a
+ * hit has no column: it sets error bit 1 and is counted in NEITHER table (its token, vote and truth-count sums are still added).
+ * A negative token count sets error bit 4: SCV_ERR_ARG at the call in HOST mode, at scv_sync in DEVICE mode.  The kernel adds such a count as 0
+ * after raising the bit, so the running sum stays monotone and no walk leaves the row; the outputs of such a call are otherwise not specified.
+ * Outputs, summed over the P x (r_end - r_begin) cells of a budget:
+ *   tie_class_hits_out   int64 [B, 1025]  (required) cells with hit and n_modes == m
+ *   token_sum_out        int64 [B]        (NULL ok) tokens actually spent
+ *   vote_count_sum_out   int64 [B]        (NULL ok) sum of n_b
+ *   truth_count_sum_out  int64 [B]        (NULL ok) votes equal to the truth in the prefixes
+ *   per_resample_out     int64 [r_end - r_begin, B, M] (NULL ok) class counts per ordering, summed over problems only (m < M; a hit with
+ *                        n_modes >= M sets error bit 1)
+ *   cells_out            scv_cell [P, B] (NULL ok; SCV_ORDER_POOL only) and cell_tokens_out int64 [P, B] (NULL ok; SCV_ORDER_POOL only): the
+ *                        cells of the cache order; OVERWRITTEN in both modes.  min_mode is the smallest modal value (clamped into the bins);
+ *                        under SCV_FLAG_OPEN_DOMAIN it is the CODE of that value (a code of up to 4095 fits the int16; engine.decode_min_mode
+ *                        turns it back); -1 in an empty cell.
+ * DEVICE mode ACCUMULATES into the per-budget outputs and per_resample_out (+=) and only enqueues: ONE launch, no allocation, no
+ * synchronisation, legal under hipGraph capture.  HOST mode overwrites, stages chunks of problems through device memory (the path the lane
+ * entries share) and blocks.  Slices of r and shards of p (p_offset) add up to the whole call bit for bit.
+ * Limits: 1 <= N <= SCV_WIDE_MAX_N, 1 <= B <= 32, 0 <= r_begin <= r_end < 2^31, p_offset >= 0, M >= 1 when per_resample_out is given.
+ * SCV_ERR_ARG with nothing queued: a NULL tokens (with P > 0), token_budget or tie_class_hits_out; a bad order; SCV_ORDER_POOL with an r-range
+ * other than [0, 1); cell outputs with SCV_ORDER_SHUFFLED; a limit broken.  One workgroup per (problem, ordering): the sort of
+ * scv_resample_wide_i32, then a workgroup-wide int64 scan writes the running token sum over the dead random bits of every sorted word, n_b
+ * is a binary search per budget, and the sorted budgets are walked over one histogram (csrc/scvote_wide_budget.hip.h).
+ */
+int scv_token_budget_wide_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens,
+                              const int64_t* token_budget, const int32_t* truth,
+                              int64_t P, int32_t B, int64_t N, int64_t p_offset, int order,
+                              int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M, int mem_kind,
+                              int64_t* tie_class_hits_out, int64_t* token_sum_out,
+                              int64_t* vote_count_sum_out, int64_t* truth_count_sum_out,
+                              int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out);
+
+/*
  * Exact expected majority vote: maj@k over ALL k-subsets of one pool per problem (new semantics, not in the reference) -- the
  * R -> infinity limit of scv_resample_prefix_i32 (the prefix of a uniformly random ordering is a uniformly random k-subset), with no
  * seed and nothing left to converge.
@@ -638,7 +688,7 @@ int scv_expected_majority_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* 
 
 /*
  * The device error word (bit 0: a vote outside bins 0..1023 -- exported as 0 under SCV_FLAG_CLAMP_TO_INVALID_BIN, where
- * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32 or scv_shortest_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 7: a draw budget above SCV_IID_MAX_DRAWS in a DEVICE-mode scv_iid_prefix_i32, which then computed nothing; bit 2: the one-launch vote +
+ * scv_sync does not treat it as an error either; bit 1: a drawn bootstrap hit, or a resampled hit with per_resample_out, had n_modes >= M; bit 4: a negative token count in scv_token_budget_prefix_i32, scv_token_budget_wide_i32 or scv_shortest_prefix_i32; bit 5: a weight outside 0 .. SCV_WEIGHT_MAX in scv_weighted_prefix_i32; bit 6: an unknown rule flag in scv_adaptive_prefix_i32; bit 7: a draw budget above SCV_IID_MAX_DRAWS in a DEVICE-mode scv_iid_prefix_i32, which then computed nothing; bit 2: the one-launch vote +
  * bootstrap of a NON-cooperative launch gave up at its grid barrier -- not an error: the next scv_sync repairs it), widened to
  * int64 and written to *dst_device IN STREAM ORDER behind everything queued so far; it is not cleared (scv_sync does
  * that).  For multi-GPU callers: the reference sums scores over problems in one process (o1.py:236-245); when the

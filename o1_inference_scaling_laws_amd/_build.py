@@ -23,8 +23,9 @@ UNIT_HEADERS = {"scvote_sort.hip": [os.path.join(CSRC, "scvote_sort.hip.h"), os.
                 "scvote_sort_prefix.hip": [os.path.join(CSRC, "scvote_sort_prefix.hip.h"), os.path.join(CSRC, "scvote_sort.hip.h"), os.path.join(CSRC, "scvote_sortnet.h")],
                 "scvote_resample.hip": [os.path.join(CSRC, "scvote_resample.hip.h"), os.path.join(CSRC, "scvote_expected.hip.h"),
                                         os.path.join(CSRC, "scvote_budget.hip.h"), os.path.join(CSRC, "scvote_weighted.hip.h"), os.path.join(CSRC, "scvote_adaptive.hip.h"),
-                                        os.path.join(CSRC, "scvote_iid.hip.h"), os.path.join(CSRC, "scvote_shortest.hip.h"), os.path.join(CSRC, "scvote_wide.hip.h")]}      # headers only one unit includes
-SOURCES = UNITS + ["scvote_hostpool.h", "scvote_kernels.hip.h", "scvote_sort.hip.h", "scvote_sortnet.h", "scvote_prefix.hip.h", "scvote_sort_prefix.hip.h", "scvote_resample.hip.h", "scvote_expected.hip.h", "scvote_budget.hip.h", "scvote_weighted.hip.h", "scvote_adaptive.hip.h", "scvote_iid.hip.h", "scvote_shortest.hip.h", "scvote_wide.hip.h", "scvote_expected_table.h", "scvote_dispatch.h", "scvote_plan.h"]          # (tools/kernel_resources.py lists them)
+                                        os.path.join(CSRC, "scvote_iid.hip.h"), os.path.join(CSRC, "scvote_shortest.hip.h"), os.path.join(CSRC, "scvote_wide.hip.h"),
+                                        os.path.join(CSRC, "scvote_wide_budget.hip.h")]}      # headers only one unit includes
+SOURCES = UNITS + ["scvote_hostpool.h", "scvote_kernels.hip.h", "scvote_sort.hip.h", "scvote_sortnet.h", "scvote_prefix.hip.h", "scvote_sort_prefix.hip.h", "scvote_resample.hip.h", "scvote_expected.hip.h", "scvote_budget.hip.h", "scvote_weighted.hip.h", "scvote_adaptive.hip.h", "scvote_iid.hip.h", "scvote_shortest.hip.h", "scvote_wide.hip.h", "scvote_wide_budget.hip.h", "scvote_expected_table.h", "scvote_dispatch.h", "scvote_plan.h"]          # (tools/kernel_resources.py lists them)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

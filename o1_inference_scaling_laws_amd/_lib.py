@@ -17,7 +17,7 @@ RULE_WEIGHT_SUM, RULE_BEST_OF = 0, 1
 STOP_DECIDED = 0x1
 WEIGHT_MAX = 2 ** 24 - 1
 IID_MAX_DRAWS = 65535
-WIDE_MAX_N = 4096                        # SCV_WIDE_MAX_N: the largest pool of scv_resample_wide_i32
+WIDE_MAX_N = 4096                        # SCV_WIDE_MAX_N: the largest pool of scv_resample_wide_i32 and scv_token_budget_wide_i32
 IID_SALT = 0xA0761D6478BD642F            # the stream salt of scv_iid_prefix_i32 (scv_resample_prefix_i32: 0xD6E8FEB86659FD93)
 ERR_BIT_IID_DRAWS = 128                  # bit 7 of the device error word
 COMM_PEER, COMM_RCCL = 0x0, 0x1
@@ -92,6 +92,8 @@ def load():
         L.scv_iid_prefix_i32.argtypes = [p, p, p, p, p, i64, i32, i64, i64, i32, i32, u64, i32, C.c_int, p, p, p, p]
     if not ab_build or hasattr(L, "scv_resample_wide_i32"):
         L.scv_resample_wide_i32.argtypes = [p, p, p, p, p, i64, i32, i64, i64, i32, i32, u64, i32, C.c_int, p, p, p, p]
+    if not ab_build or hasattr(L, "scv_token_budget_wide_i32"):
+        L.scv_token_budget_wide_i32.argtypes = [p, p, p, p, p, i64, i32, i64, i64, C.c_int, i32, i32, u64, i32, C.c_int, p, p, p, p, p, p, p]
     L.scv_last_kernel_ns.argtypes = [p, C.POINTER(u64)]
     L.scv_drain_kernel_ns.argtypes = [p, C.POINTER(u64), C.POINTER(u64)]
     L.scv_get_stat.argtypes = [p, C.c_char_p, C.POINTER(i64)]
@@ -104,7 +106,7 @@ def load():
     L.scv_version.argtypes = []
     L.scv_version.restype = C.c_char_p
     for name in ("scv_create", "scv_destroy", "scv_set_stream", "scv_sync", "scv_set_tuning", "scv_set_option", "scv_aggregate_i32", "scv_aggregate_prefix_i32",
-                 "scv_bootstrap", "scv_aggregate_bootstrap_i32", "scv_synth_fill_i32", "scv_resample_prefix_i32", "scv_expected_majority_i32", "scv_token_budget_prefix_i32", "scv_weighted_prefix_i32", "scv_adaptive_prefix_i32", "scv_shortest_prefix_i32", "scv_iid_prefix_i32", "scv_resample_wide_i32", "scv_last_kernel_ns", "scv_drain_kernel_ns",
+                 "scv_bootstrap", "scv_aggregate_bootstrap_i32", "scv_synth_fill_i32", "scv_resample_prefix_i32", "scv_expected_majority_i32", "scv_token_budget_prefix_i32", "scv_weighted_prefix_i32", "scv_adaptive_prefix_i32", "scv_shortest_prefix_i32", "scv_iid_prefix_i32", "scv_resample_wide_i32", "scv_token_budget_wide_i32", "scv_last_kernel_ns", "scv_drain_kernel_ns",
                  "scv_device_count", "scv_device_info", "scv_host_alloc", "scv_host_free", "scv_get_stat", "scv_export_error_word",
                  "scv_comm_create", "scv_comm_destroy", "scv_comm_size", "scv_allreduce_counters", "scv_comm_sync",
                  "scv_allgather_cells", "scv_allgather_i64", "scv_comm_get_stat"):

@@ -1503,13 +1503,52 @@ int launch_wide(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const 
     return SCV_OK;
 }
 
+// scv_token_budget_wide_i32 on device pointers: one launch of the wide token-budget body of scv_resample_prefix<false>
+// (scvote_wide_budget.hip.h), accumulating into the per-budget outputs and overwriting the cells.  The geometry of launch_wide: one workgroup per
+// (problem, ordering) item, wide_lanes(N) lanes, a persistent grid of as many workgroups as stay resident; the LDS is wide_budget_lds_words
+// (224 + 8 B bytes above the wide call's: 51 KiB at N = 4096 with 12 budgets, 55 KiB on a SCV_FLAG_OPEN_DOMAIN context).
+int launch_wide_budget(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* budgets, const int32_t* truth,
+                       int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed,
+                       int32_t M, int64_t* tie, int64_t* tok_sum, int64_t* vote_sum, int64_t* truth_sum, int64_t* per_resample,
+                       scv_cell* cells, int64_t* cell_tokens, uint32_t* err) {
+    if (P == 0 || r_end == r_begin) return SCV_OK;
+    scv::ResampleArgs a = lane_args(pool, tokens, nullptr, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie, tok_sum, truth_sum,
+                                    per_resample, err);
+    a.mode = scv::kResampleModeWideBudget;
+    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;        // (its own launch: not through launch_lane_body)
+    a.budgets = budgets;
+    a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
+    a.cells_out = cells; a.cell_tokens_out = cell_tokens;
+    const scv::ResampleFn fn = pick_resample_kernel(false);
+    const int lanes = scv::wide_lanes((int)N);
+    const size_t lds = (size_t)scv::wide_budget_lds_words((int)N, B, a.open_domain != 0) * sizeof(uint32_t);
+    if ((int64_t)lds > ctx->lds_max) return fail(SCV_ERR_ARG, "token_budget_wide: N=%d B=%d does not fit the LDS of one workgroup", a.N, a.B);
+    SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+    int per_cu = 0;
+    SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds));
+    if (per_cu < 1) per_cu = 1;
+    const int64_t items = P * a.R;
+    int64_t grid = (int64_t)ctx->num_cus * per_cu;
+    if (grid > items) grid = items;
+    if (ctx->grid_override > 0) grid = ctx->grid_override;
+    EventPair* ev = nullptr;
+    if (int rc = next_event_pair(ctx, &ev)) return rc;
+    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)lanes), lds, ctx->stream, a);
+    SCV_HIP(hipGetLastError());
+    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
+    ctx->err_dirty = true;
+    return SCV_OK;
+}
+
 // The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32, scv_adaptive_prefix_i32,
 // scv_shortest_prefix_i32 and scv_iid_prefix_i32 share, in
 // the order the entries have always made them; `what` names the entry in every message.  An entry's own checks keep their places in that
 // order: `early` runs behind the shape check (weighted: the rule), `own` behind the P * R bound (the pointers the entry requires).
 // cells_given: the cell outputs of the entry as its message lists them when the caller passed one, NULL when it passed none.
 // scv_resample_prefix_i32 has neither an order nor cells: it passes SCV_ORDER_SHUFFLED and NULL.  n_max: the largest pool of the entry (the lane
-// bodies: kResampleMaxN; scv_resample_wide_i32, which shares the checks and the staging but not the lane layout: SCV_WIDE_MAX_N).
+// bodies: kResampleMaxN; scv_resample_wide_i32 and scv_token_budget_wide_i32, which share the checks and the staging but not the lane layout:
+// SCV_WIDE_MAX_N; the second also passes its order and its cells, as scv_token_budget_prefix_i32 does).
 template <class Early, class Own>
 int check_lane_call(const char* what, const scv_ctx* ctx, int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin,
                     int32_t r_end, const char* cells_given, bool per_resample, int32_t M, int mem_kind, Early early, Own own,
@@ -2031,6 +2070,39 @@ int scv_resample_wide_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* toke
             return launch_wide(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[NV].at<const int32_t>(),
                                rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
                                rg[TSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(), err);
+        });
+    });
+}
+
+int scv_token_budget_wide_i32(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int64_t* token_budget, const int32_t* truth,
+                              int64_t P, int32_t B, int64_t N, int64_t p_offset, int order, int32_t r_begin, int32_t r_end, uint64_t seed,
+                              int32_t M, int mem_kind, int64_t* tie_class_hits_out, int64_t* token_sum_out, int64_t* vote_count_sum_out,
+                              int64_t* truth_count_sum_out, int64_t* per_resample_out, scv_cell* cells_out, int64_t* cell_tokens_out) {
+    return guarded([&]() -> int {
+        const char* cells_given = (cells_out || cell_tokens_out) ? "cells_out / cell_tokens_out" : nullptr;
+        if (int rc = check_lane_call("token_budget_wide", ctx, P, B, N, p_offset, order, r_begin, r_end, cells_given, per_resample_out, M, mem_kind, no_check, [&] {
+                if (!token_budget || !tie_class_hits_out) return fail(SCV_ERR_ARG, "token_budget_wide: token_budget and tie_class_hits_out are required");
+                if (P > 0 && (!pool || !tokens || !truth)) return fail(SCV_ERR_ARG, "token_budget_wide: pool, tokens and truth are required");
+                return SCV_OK;
+            }, SCV_WIDE_MAX_N)) return rc;
+        SCV_ENTER(ctx);
+        if (!per_resample_out) M = 1;
+        if (mem_kind == SCV_MEM_DEVICE)
+            return launch_wide_budget(ctx, pool, tokens, token_budget, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M,
+                                      tie_class_hits_out, token_sum_out, vote_count_sum_out, truth_count_sum_out, per_resample_out, cells_out,
+                                      cell_tokens_out, ctx->d_err);
+        const size_t row = (size_t)N * sizeof(int32_t), sums = (size_t)B * sizeof(int64_t);
+        enum { POOL, TOK, TRUTH, BUD, CELLS, CTOK, TIE, TSUM, VSUM, TCS, PER };
+        Region rg[] = {rows_in(pool, row), rows_in(tokens, row), rows_in(truth, sizeof(int32_t)), once_in(token_budget, (size_t)B * sizeof(int64_t)),
+                       rows_out(cells_out, (size_t)B * sizeof(scv_cell)), rows_out(cell_tokens_out, sums),
+                       sums_out(tie_class_hits_out, sums * SCV_TIE_CLASSES), sums_out(token_sum_out, sums), sums_out(vote_count_sum_out, sums),
+                       sums_out(truth_count_sum_out, sums), sums_out(per_resample_out, (size_t)(r_end - r_begin) * M * sums)};
+        if (P == 0 || r_end == r_begin) return zero_outputs(rg, PER + 1, P);       // HOST mode overwrites: nothing voted, all zero
+        return stage_call(ctx, rg, PER + 1, P, kStageChunkBytes, [&](int64_t np, int64_t p0, uint32_t* err) {     // (sums add: chunks of problems)
+            return launch_wide_budget(ctx, rg[POOL].at<const int32_t>(), rg[TOK].at<const int32_t>(), rg[BUD].at<const int64_t>(),
+                                      rg[TRUTH].at<const int32_t>(), np, B, N, p_offset + p0, order, r_begin, r_end, seed, M, rg[TIE].at<int64_t>(),
+                                      rg[TSUM].at<int64_t>(), rg[VSUM].at<int64_t>(), rg[TCS].at<int64_t>(), rg[PER].at<int64_t>(),
+                                      rg[CELLS].at<scv_cell>(), rg[CTOK].at<int64_t>(), err);
         });
     });
 }

@@ -105,7 +105,7 @@ struct ResampleArgs {
 };
 using ResampleFn = void (*)(const ResampleArgs);
 constexpr int32_t kResampleModeShuffle = 0, kResampleModeExpected = 1, kResampleModeTokenBudget = 2, kResampleModeWeighted = 3,
-                  kResampleModeAdaptive = 4, kResampleModeIid = 5, kResampleModeShortest = 6, kResampleModeWide = 7;
+                  kResampleModeAdaptive = 4, kResampleModeIid = 5, kResampleModeShortest = 6, kResampleModeWide = 7, kResampleModeWideBudget = 8;
 constexpr int32_t kOrderPool = 0, kOrderShuffled = 1;    // SCV_ORDER_POOL / SCV_ORDER_SHUFFLED (include/scvote.h)
 // LDS words of a token-budget workgroup (scvote_budget.hip.h, in this order): sorted budgets (32 int64) | per-budget sums (3 B int64) |
 // budget order [32] | tie classes [B][N + 1] | per-wave encoding scratch (64 each) | per-row truth code and distinct count [np_max][2] |
@@ -175,6 +175,14 @@ constexpr int wide_tie_cols(int N) { return (N < 127 ? N : 127) + 1; }
 constexpr long long wide_hist_words(int N, bool open) { return open ? ((N > kBins ? N : kBins) + 1) / 2 : kBins; }
 constexpr long long wide_lds_words(int N, int B, bool open) {
     return 2LL * wide_pad(N) + 4LL * B + 16 + wide_hist_words(N, open) + (long long)B * wide_tie_cols(N) + 16 + 64 + (N + 1) / 2;
+}
+// LDS words of a wide token-budget workgroup (scv_token_budget_wide_i32, scvote_wide_budget.hip.h; mode kResampleModeWideBudget of the <false>
+// instantiation; the kernel's layout, in this order): the sort words, later running sum << 12 | index (wide_pad(N) uint64) | per-budget sums
+// (3 B int64: truth counts, tokens, votes) | sorted budgets (32 int64) | the waves' token sums of the scan (4 int64) | the histogram
+// (wide_hist_words) | tie classes [B][wide_tie_cols(N)] | the waves' (largest count << 12 | 4095 - its smallest bin, modes) (2 x 4 x 2) | the item's prefix lengths and
+// the budgets' order (2 x 32) | the row as 16-bit bins [N].  224 + 8 B bytes more than wide_lds_words.
+constexpr long long wide_budget_lds_words(int N, int B, bool open) {
+    return 2LL * wide_pad(N) + 6LL * B + 64 + 8 + wide_hist_words(N, open) + (long long)B * wide_tie_cols(N) + 16 + 64 + (N + 1) / 2;
 }
 ResampleFn pick_resample_kernel(bool tok);
 

@@ -29,10 +29,11 @@
 //    no allocation: a DEVICE-mode call is one launch and may be captured into a graph.
 //
 // LDS per lane 2 * 4 * ceil(N / 4) bytes (N = 128: 16 KiB per wave, 10 waves per CU of 160 KiB; N = 256: 32 KiB per wave, 5 waves).
-// The <false> instantiation has four more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h),
+// The <false> instantiation has five more bodies: the exact form of the same expectation (mode kResampleModeExpected, scvote_expected.hip.h),
 // the weighted vote / best-of-N (mode kResampleModeWeighted, scvote_weighted.hip.h), the vote over draws with replacement (mode
-// kResampleModeIid, scvote_iid.hip.h) and the sorted orderings of pools of up to 4096 samples (mode kResampleModeWide, scvote_wide.hip.h,
-// workgroup-cooperative like the exact form); the <true> one the vote over the longest prefix
+// kResampleModeIid, scvote_iid.hip.h), the sorted orderings of pools of up to 4096 samples (mode kResampleModeWide, scvote_wide.hip.h,
+// workgroup-cooperative like the exact form) and the token budgets over those orderings (mode kResampleModeWideBudget,
+// scvote_wide_budget.hip.h); the <true> one the vote over the longest prefix
 // that fits a token budget (mode kResampleModeTokenBudget, scvote_budget.hip.h), the vote that stops by a rule on its own state
 // (mode kResampleModeAdaptive, scvote_adaptive.hip.h) and the vote over the m shortest of the first k samples (mode kResampleModeShortest,
 // scvote_shortest.hip.h).
@@ -203,6 +204,7 @@ __device__ __forceinline__ int32_t resample_min_mode(const ResampleArgs& a, int6
 #include "scvote_shortest.hip.h"
 #include "scvote_iid.hip.h"
 #include "scvote_wide.hip.h"
+#include "scvote_wide_budget.hip.h"
 
 namespace scv {
 
@@ -214,6 +216,7 @@ __global__ __launch_bounds__(kResampleMaxLanes) void scv_resample_prefix(const R
         if (a.mode == kResampleModeWeighted) { weighted_body(a, smem_wg); return; }             // weighted vote / best-of-N: scvote_weighted.hip.h
         if (a.mode == kResampleModeIid) { iid_body(a, smem_wg); return; }                       // draws with replacement: scvote_iid.hip.h
         if (a.mode == kResampleModeWide) { wide_body(a, smem_wg); return; }                     // pools of up to 4096 samples: scvote_wide.hip.h
+        if (a.mode == kResampleModeWideBudget) { wide_budget_body(a, smem_wg); return; }        // ... under token budgets: scvote_wide_budget.hip.h
     } else {
         if (a.mode == kResampleModeTokenBudget) { token_budget_body(a, smem_wg); return; }      // token budgets: scvote_budget.hip.h
         if (a.mode == kResampleModeAdaptive) { adaptive_body(a, smem_wg); return; }             // stopping rules: scvote_adaptive.hip.h

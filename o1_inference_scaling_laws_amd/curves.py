@@ -89,6 +89,25 @@ def token_budget_records(engine, pool, truth, tokens, token_limits, resamples: i
             for b, t in enumerate(limits)]
 
 
+def wide_token_budget_records(engine, pool, truth, tokens, token_limits, resamples: int | None = None, seed: int = 0):
+    """``token_budget_records`` for caches of up to WIDE_MAX_N = 4096 samples per problem (Engine.token_budget_wide,
+    scv_token_budget_wide_i32): pool / tokens int32 [P, Npool], truth int32 [P].  For every token limit T -- any number of them; the engine
+    takes 32 per call -- the accuracy of the majority vote over the longest prefix whose tokens fit T, in the cache order (``resamples=None``)
+    or averaged over ``resamples`` sorted-key orderings, the tokens it spent and the samples it voted over, as records {'token_limit',
+    'accuracy', 'avg_tokens_used', 'avg_votes'}: the token axis of o1.py:266-283 up to 2^22 and beyond.  At Npool <= 256 the shuffled
+    orderings differ from those of ``token_budget_records`` (only the expectation is shared); the cache order gives the same records."""
+    limits = [int(t) for t in token_limits]
+    pool = np.asarray(pool, dtype=np.int32)
+    tokens = np.asarray(tokens, dtype=np.int32)
+    recs = []
+    for i in range(0, len(limits), 32):
+        part = limits[i:i + 32]
+        res = engine.token_budget_wide(pool, tokens, truth, np.array(part, dtype=np.int64), resamples=resamples, seed=seed, M=0)
+        recs += [{"token_limit": t, "accuracy": res.accuracy(b), "avg_tokens_used": float(res.avg_tokens_used(b)), "avg_votes": float(res.avg_votes(b))}
+                 for b, t in enumerate(part)]
+    return recs
+
+
 def shortest_vote_records(engine, pool, truth, tokens, pairs, resamples: int | None = None, seed: int = 0):
     """pool / tokens int32 [P, Npool] (each problem's samples in cache order), truth int32 [P], ``pairs`` a list of (k, m).  For every pair:
     the accuracy of short-m@k -- k samples in parallel, the vote over the m that finish first (Engine.shortest_prefix,

@@ -436,6 +436,37 @@ class Engine:
                                                   _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
         return TokenBudgetResult(P, R, tie, tok, votes, tcs, per, cells, cell_tokens)
 
+    def token_budget_wide(self, pool, tokens, truth, token_budgets, resamples: int | None = None, seed: int = 0, r_begin: int = 0,
+                          p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> TokenBudgetResult:
+        """Majority vote over the longest prefix of each ordering of a pool of up to WIDE_MAX_N = 4096 samples that fits a token budget
+        (scv_token_budget_wide_i32; CPU mirror: wide_budget.py).  The signature and the result of ``token_budget_prefix``; the shuffled
+        orderings are those of ``resample_wide`` (sort keys), NOT those of ``token_budget_prefix`` -- in pool order (``resamples=None``) the
+        two agree in every output at N <= 256.  pool / tokens int32 [P, N] (numpy), truth [P], token_budgets int64 [B] (B <= 32, any order).
+        ``M``: classes of ``per_resample`` (None: min(N, 1024) + 1, which no counted hit can exceed; 0: not computed).  Blocking.  On an
+        ``Engine(open_domain=True)`` every int32 is a value of its own and ``cells["min_mode"]`` is a code (``decode_min_mode``); a hit that
+        ties 1025 or more ways raises ScvError (ERR_ARG)."""
+        pool, _, P, N, r0, r1, _, order = _host_orderings(pool, None, resamples, r_begin, M, want_cells)
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        budgets = np.ascontiguousarray(token_budgets, dtype=np.int64)
+        if tokens.shape != pool.shape or truth.shape != (P,) or budgets.ndim != 1:
+            raise ValueError("tokens must match pool, truth must be [P] and token_budgets [B]")
+        B = budgets.shape[0]
+        R = r1 - r0
+        if M is None:
+            M = min(N, TIE_CLASSES - 1) + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64)
+        votes = np.zeros((B,), dtype=np.int64)
+        tcs = np.zeros((B,), dtype=np.int64)
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
+        cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
+        check(self._L.scv_token_budget_wide_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N,
+                                                p_offset, order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok),
+                                                _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
+        return TokenBudgetResult(P, R, tie, tok, votes, tcs, per, cells, cell_tokens)
+
     def weighted_prefix(self, pool, weights, truth, n_valid, rule: int = _lib.RULE_WEIGHT_SUM, resamples: int | None = None, seed: int = 0,
                         r_begin: int = 0, p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False) -> WeightedResult:
         """Weighted majority vote (``rule`` RULE_WEIGHT_SUM) or best-of-N (RULE_BEST_OF) over the first n_valid[b] samples of each pool
@@ -777,6 +808,35 @@ class Engine:
                                                   r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits),
                                                   _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(per_resample), _ptr(cells),
                                                   _ptr(cell_tokens)))
+        return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
+
+    def token_budget_wide_device(self, pool, tokens, truth, token_budgets, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
+                                 p_offset: int = 0, tie_class_hits=None, token_sum=None, vote_count_sum=None, truth_count_sum=None,
+                                 per_resample=None, M: int | None = None, cells=None, cell_tokens=None, want_cells: bool = False):
+        """DEVICE-mode token_budget_wide: pool / tokens torch.int32 cuda [P, N] (N <= 4096), truth [P], token_budgets torch.int64 [B].
+        ``r_end=None``: the pool's own order (r_begin must be 0); otherwise the orderings [r_begin, r_end) of resample_wide.  ACCUMULATES into
+        the given int64 buffers (tie_class_hits [B, 1025], token_sum, vote_count_sum, truth_count_sum [B], per_resample [r_end - r_begin, B, M];
+        those left None are allocated zeroed -- per_resample only when ``M`` is given).  Pool order only: OVERWRITES cells (uint8 [P, B, 16])
+        and cell_tokens (int64 [P, B]), allocated when ``want_cells``.  One launch on torch's current stream, does not synchronise, may be
+        captured into a graph (a negative token count, a hit with n_modes >= M or -- open domain -- >= 1025 is reported by ``sync``).
+        Returns (tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens)."""
+        import torch
+        i32, i64 = torch.int32, torch.int64
+        B = int(token_budgets.shape[0])
+        P, N, dev, r_end, order, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("tokens", tokens, "PN", i32, False), ("truth", truth, "P", i32, False), ("token_budgets", token_budgets, "B", i64, False)),
+            r_begin, r_end, tie_class_hits, per_resample, M, labels=(None, None))
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", i64, dev, alloc=torch.zeros)
+        vote_count_sum = _device_tensor(vote_count_sum, (B,), "vote_count_sum", i64, dev, alloc=torch.zeros)
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", i64, dev, alloc=torch.zeros)
+        if want_cells or cells is not None:
+            cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
+        if want_cells or cell_tokens is not None:
+            cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
+        check(self._L.scv_token_budget_wide_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(token_budgets), _ptr(truth), P, B, N, p_offset, order,
+                                                r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits),
+                                                _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(per_resample), _ptr(cells),
+                                                _ptr(cell_tokens)))
         return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
 
     def shortest_prefix_device(self, pool, tokens, truth, n_valid, m_keep, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
