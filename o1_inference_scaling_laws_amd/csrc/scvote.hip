@@ -1468,10 +1468,34 @@ int launch_iid(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const i
                             [&](int lanes, int np) { return scv::iid_lds_words((int)N, B, lanes, np); }, "iid", nullptr);
 }
 
+// The launch that the two wide entries share, behind the filling of `a`: one workgroup of wide_lanes(N) lanes per (problem, ordering) item with
+// lds_bytes of LDS, a persistent grid of as many workgroups as stay resident, each with a contiguous run of items.  Not through
+// launch_lane_body: no lanes to choose, no rows per chunk.  `what` names the entry in the refusal.
+int launch_wide_items(scv_ctx* ctx, const scv::ResampleArgs& a, size_t lds_bytes, const char* what) {
+    const scv::ResampleFn fn = pick_resample_kernel(false);
+    const int lanes = scv::wide_lanes(a.N);
+    if ((int64_t)lds_bytes > ctx->lds_max) return fail(SCV_ERR_ARG, "%s: N=%d B=%d does not fit the LDS of one workgroup", what, a.N, a.B);
+    SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+    int per_cu = 0;
+    SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds_bytes));
+    if (per_cu < 1) per_cu = 1;
+    const int64_t items = a.P * a.R;
+    int64_t grid = (int64_t)ctx->num_cus * per_cu;
+    if (grid > items) grid = items;
+    if (ctx->grid_override > 0) grid = ctx->grid_override;
+    EventPair* ev = nullptr;
+    if (int rc = next_event_pair(ctx, &ev)) return rc;
+    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)lanes), lds_bytes, ctx->stream, a);
+    SCV_HIP(hipGetLastError());
+    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
+    ctx->err_dirty = true;
+    return SCV_OK;
+}
+
 // scv_resample_wide_i32 on device pointers: one launch of the wide body of scv_resample_prefix<false> (scvote_wide.hip.h), accumulating into the
 // outputs.  One workgroup per (problem, resample) item, its size and its LDS from N (wide_lanes, wide_lds_words: 51 KiB at N = 4096 with 13
-// budgets, 61 KiB with 32 -- every N in range fits one workgroup); a persistent grid of as many workgroups as stay resident, each with a
-// contiguous run of items.  Not through launch_lane_body: no lanes to choose, no rows per chunk.  On a SCV_FLAG_OPEN_DOMAIN context the body
+// budgets, 61 KiB with 32 -- every N in range fits one workgroup), launched by launch_wide_items.  On a SCV_FLAG_OPEN_DOMAIN context the body
 // encodes its rows by value and its histogram holds max(1024, N) 16-bit counts (55 KiB at N = 4096 with 13 budgets, 65 KiB with 32).
 int launch_wide(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const int32_t* n_valid, const int32_t* truth,
                 int64_t P, int32_t B, int64_t N, int64_t p_offset, int32_t r_begin, int32_t r_end, uint64_t seed, int32_t M,
@@ -1480,27 +1504,8 @@ int launch_wide(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens, const 
     scv::ResampleArgs a = lane_args(pool, tokens, n_valid, truth, P, B, N, p_offset, SCV_ORDER_SHUFFLED, r_begin, r_end, seed, M, tie, tok_sum,
                                     truth_sum, per_resample, err);
     a.mode = scv::kResampleModeWide;
-    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;        // (its own launch: not through launch_lane_body)
-    const scv::ResampleFn fn = pick_resample_kernel(false);
-    const int lanes = scv::wide_lanes((int)N);
-    const size_t lds = (size_t)scv::wide_lds_words((int)N, B, a.open_domain != 0) * sizeof(uint32_t);
-    if ((int64_t)lds > ctx->lds_max) return fail(SCV_ERR_ARG, "resample_wide: N=%d B=%d does not fit the LDS of one workgroup", a.N, a.B);
-    SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-    int per_cu = 0;
-    SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds));
-    if (per_cu < 1) per_cu = 1;
-    const int64_t items = P * a.R;
-    int64_t grid = (int64_t)ctx->num_cus * per_cu;
-    if (grid > items) grid = items;
-    if (ctx->grid_override > 0) grid = ctx->grid_override;
-    EventPair* ev = nullptr;
-    if (int rc = next_event_pair(ctx, &ev)) return rc;
-    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)lanes), lds, ctx->stream, a);
-    SCV_HIP(hipGetLastError());
-    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
-    ctx->err_dirty = true;
-    return SCV_OK;
+    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;
+    return launch_wide_items(ctx, a, (size_t)scv::wide_lds_words((int)N, B, a.open_domain != 0) * sizeof(uint32_t), "resample_wide");
 }
 
 // scv_token_budget_wide_i32 on device pointers: one launch of the wide token-budget body of scv_resample_prefix<false>
@@ -1515,30 +1520,11 @@ int launch_wide_budget(scv_ctx* ctx, const int32_t* pool, const int32_t* tokens,
     scv::ResampleArgs a = lane_args(pool, tokens, nullptr, truth, P, B, N, p_offset, order, r_begin, r_end, seed, M, tie, tok_sum, truth_sum,
                                     per_resample, err);
     a.mode = scv::kResampleModeWideBudget;
-    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;        // (its own launch: not through launch_lane_body)
+    a.open_domain = (ctx->flags & SCV_FLAG_OPEN_DOMAIN) ? 1 : 0;
     a.budgets = budgets;
     a.vote_sum = reinterpret_cast<unsigned long long*>(vote_sum);
     a.cells_out = cells; a.cell_tokens_out = cell_tokens;
-    const scv::ResampleFn fn = pick_resample_kernel(false);
-    const int lanes = scv::wide_lanes((int)N);
-    const size_t lds = (size_t)scv::wide_budget_lds_words((int)N, B, a.open_domain != 0) * sizeof(uint32_t);
-    if ((int64_t)lds > ctx->lds_max) return fail(SCV_ERR_ARG, "token_budget_wide: N=%d B=%d does not fit the LDS of one workgroup", a.N, a.B);
-    SCV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-    int per_cu = 0;
-    SCV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), lanes, lds));
-    if (per_cu < 1) per_cu = 1;
-    const int64_t items = P * a.R;
-    int64_t grid = (int64_t)ctx->num_cus * per_cu;
-    if (grid > items) grid = items;
-    if (ctx->grid_override > 0) grid = ctx->grid_override;
-    EventPair* ev = nullptr;
-    if (int rc = next_event_pair(ctx, &ev)) return rc;
-    if (ev) SCV_HIP(hipEventRecord(ev->a, ctx->stream));
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)lanes), lds, ctx->stream, a);
-    SCV_HIP(hipGetLastError());
-    if (ev) SCV_HIP(hipEventRecord(ev->b, ctx->stream));
-    ctx->err_dirty = true;
-    return SCV_OK;
+    return launch_wide_items(ctx, a, (size_t)scv::wide_budget_lds_words((int)N, B, a.open_domain != 0) * sizeof(uint32_t), "token_budget_wide");
 }
 
 // The argument checks that scv_resample_prefix_i32, scv_token_budget_prefix_i32, scv_weighted_prefix_i32, scv_adaptive_prefix_i32,

@@ -307,6 +307,25 @@ class Engine:
         check(self._L.scv_bootstrap(self._ctx, _np_ptr(cells), P, B, r_begin, r_end, seed, M, _lib.MEM_HOST, _np_ptr(out)))
         return out
 
+    def _host_resample(self, fn, budget_name, pool, truth, budgets, resamples, seed, tokens, r_begin, p_offset, M) -> ResampleResult:
+        """The HOST-mode body that resample_prefix, resample_wide and iid_prefix share: ``fn`` is the entry of the library (one argument list),
+        ``budget_name`` names the budget argument in the ValueError."""
+        pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        budgets = np.ascontiguousarray(budgets, dtype=np.int32)
+        if truth.shape != (P,) or budgets.ndim != 1:
+            raise ValueError(f"truth must be [P] and {budget_name} [B]")
+        B = budgets.shape[0]
+        R = r1 - r0
+        if M is None:
+            M = int(np.clip(budgets, 0, N).max(initial=0)) + 1
+        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
+        tok = np.zeros((B,), dtype=np.int64)
+        tcs = np.zeros((B,), dtype=np.int64)
+        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
+        check(fn(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N, p_offset, r0, r1, seed, M if M else 1,
+                 _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
+        return ResampleResult(P, R, tie, tok, tcs, per)
 
     def resample_prefix(self, pool, truth, n_valid, resamples: int, seed: int, tokens=None, r_begin: int = 0, p_offset: int = 0,
                         M: int | None = None) -> ResampleResult:
@@ -314,23 +333,7 @@ class Engine:
         resample.py).  pool int32 [P, N] (numpy, N <= 256), n_valid int32 [B] (B <= 32): budget b votes over the first n_valid[b]
         votes of each ordering r in [r_begin, r_begin + resamples).  Every denominator of the result is P * resamples.
         ``M``: classes of ``per_resample`` (None: max budget + 1, which no hit can exceed; 0: per_resample is not computed).  Blocking."""
-        pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
-        truth = np.ascontiguousarray(truth, dtype=np.int32)
-        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
-        if truth.shape != (P,) or n_valid.ndim != 1:
-            raise ValueError("truth must be [P] and n_valid [B]")
-        B = n_valid.shape[0]
-        R = r1 - r0
-        if M is None:
-            M = int(np.clip(n_valid, 0, N).max(initial=0)) + 1
-        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-        tok = np.zeros((B,), dtype=np.int64)
-        tcs = np.zeros((B,), dtype=np.int64)
-        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
-        check(self._L.scv_resample_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth), P, B, N, p_offset,
-                                              r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
-                                              _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
-        return ResampleResult(P, R, tie, tok, tcs, per)
+        return self._host_resample(self._L.scv_resample_prefix_i32, "n_valid", pool, truth, n_valid, resamples, seed, tokens, r_begin, p_offset, M)
 
     def resample_wide(self, pool, truth, n_valid, resamples: int, seed: int, tokens=None, r_begin: int = 0, p_offset: int = 0,
                       M: int | None = None) -> ResampleResult:
@@ -341,23 +344,7 @@ class Engine:
         exceed; 0: per_resample is not computed).  Blocking.  On an ``Engine(open_domain=True)`` every int32 is a value of its own (up to N
         distinct values per row, no domain error); a hit that ties 1025 or more ways has no column in ``tie_class_hits`` and raises
         ScvError (ERR_ARG)."""
-        pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
-        truth = np.ascontiguousarray(truth, dtype=np.int32)
-        n_valid = np.ascontiguousarray(n_valid, dtype=np.int32)
-        if truth.shape != (P,) or n_valid.ndim != 1:
-            raise ValueError("truth must be [P] and n_valid [B]")
-        B = n_valid.shape[0]
-        R = r1 - r0
-        if M is None:
-            M = int(np.clip(n_valid, 0, N).max(initial=0)) + 1
-        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-        tok = np.zeros((B,), dtype=np.int64)
-        tcs = np.zeros((B,), dtype=np.int64)
-        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
-        check(self._L.scv_resample_wide_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_valid), _np_ptr(truth), P, B, N, p_offset,
-                                            r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
-                                            _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
-        return ResampleResult(P, R, tie, tok, tcs, per)
+        return self._host_resample(self._L.scv_resample_wide_i32, "n_valid", pool, truth, n_valid, resamples, seed, tokens, r_begin, p_offset, M)
 
     def iid_prefix(self, pool, truth, n_draws, resamples: int, seed: int, tokens=None, r_begin: int = 0, p_offset: int = 0,
                    M: int | None = None) -> ResampleResult:
@@ -366,23 +353,7 @@ class Engine:
         max(n_draws[b], 0) draws -- not clamped to N, at most IID_MAX_DRAWS -- of each resample r in [r_begin, r_begin + resamples).
         Every denominator of the result is P * resamples.  ``M``: classes of ``per_resample`` (None: min(max budget, N) + 1, which no hit
         can exceed; 0: per_resample is not computed).  Blocking."""
-        pool, tokens, P, N, r0, r1, _, _ = _host_orderings(pool, tokens, resamples, r_begin, M, False)
-        truth = np.ascontiguousarray(truth, dtype=np.int32)
-        n_draws = np.ascontiguousarray(n_draws, dtype=np.int32)
-        if truth.shape != (P,) or n_draws.ndim != 1:
-            raise ValueError("truth must be [P] and n_draws [B]")
-        B = n_draws.shape[0]
-        R = r1 - r0
-        if M is None:
-            M = int(np.clip(n_draws, 0, N).max(initial=0)) + 1
-        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-        tok = np.zeros((B,), dtype=np.int64)
-        tcs = np.zeros((B,), dtype=np.int64)
-        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
-        check(self._L.scv_iid_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(n_draws), _np_ptr(truth), P, B, N, p_offset,
-                                         r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie),
-                                         _np_ptr(tok) if tokens is not None else None, _np_ptr(tcs), _np_ptr(per)))
-        return ResampleResult(P, R, tie, tok, tcs, per)
+        return self._host_resample(self._L.scv_iid_prefix_i32, "n_draws", pool, truth, n_draws, resamples, seed, tokens, r_begin, p_offset, M)
 
     def expected_majority(self, pool, truth, n_valid, tokens=None, hit_prob: bool = True) -> ExpectedResult:
         """Exact expected majority vote over all k-subsets of each pool (scv_expected_majority_i32; CPU statement: expected.py).
@@ -409,14 +380,10 @@ class Engine:
                                                 _np_ptr(score), _np_ptr(hit)))
         return ExpectedResult(score, hit, np.clip(n_valid.astype(np.int64), 0, N), N, token_total)
 
-    def token_budget_prefix(self, pool, tokens, truth, token_budgets, resamples: int | None = None, seed: int = 0, r_begin: int = 0,
-                            p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> TokenBudgetResult:
-        """Majority vote over the longest prefix of each pool ordering that fits a token budget (scv_token_budget_prefix_i32; CPU mirror:
-        token_budget.py).  pool / tokens int32 [P, N] (numpy, N <= 256), truth [P], token_budgets int64 [B] (B <= 32, any order).
-        ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells and cell tokens); otherwise the orderings
-        r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of ``per_resample`` (None: N + 1, which no hit can exceed;
-        0: not computed).  Blocking."""
-        pool, _, P, N, r0, r1, M, order = _host_orderings(pool, None, resamples, r_begin, M, want_cells)
+    def _host_token_budget(self, fn, default_M, pool, tokens, truth, token_budgets, resamples, seed, r_begin, p_offset, M, want_cells) -> TokenBudgetResult:
+        """The HOST-mode body that token_budget_prefix and token_budget_wide share: ``fn`` is the entry of the library (one argument list),
+        ``default_M(N)`` the classes of ``per_resample`` when ``M`` is None."""
+        pool, _, P, N, r0, r1, _, order = _host_orderings(pool, None, resamples, r_begin, M, want_cells)
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         truth = np.ascontiguousarray(truth, dtype=np.int32)
         budgets = np.ascontiguousarray(token_budgets, dtype=np.int64)
@@ -424,6 +391,8 @@ class Engine:
             raise ValueError("tokens must match pool, truth must be [P] and token_budgets [B]")
         B = budgets.shape[0]
         R = r1 - r0
+        if M is None:
+            M = default_M(N)
         tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
         tok = np.zeros((B,), dtype=np.int64)
         votes = np.zeros((B,), dtype=np.int64)
@@ -431,10 +400,19 @@ class Engine:
         per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
         cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
         cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
-        check(self._L.scv_token_budget_prefix_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N,
-                                                  p_offset, order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok),
-                                                  _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
+        check(fn(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N, p_offset, order, r0, r1, seed, M if M else 1,
+                 _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok), _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
         return TokenBudgetResult(P, R, tie, tok, votes, tcs, per, cells, cell_tokens)
+
+    def token_budget_prefix(self, pool, tokens, truth, token_budgets, resamples: int | None = None, seed: int = 0, r_begin: int = 0,
+                            p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> TokenBudgetResult:
+        """Majority vote over the longest prefix of each pool ordering that fits a token budget (scv_token_budget_prefix_i32; CPU mirror:
+        token_budget.py).  pool / tokens int32 [P, N] (numpy, N <= 256), truth [P], token_budgets int64 [B] (B <= 32, any order).
+        ``resamples=None``: the pool's own order (one draw; ``want_cells`` returns its cells and cell tokens); otherwise the orderings
+        r in [r_begin, r_begin + resamples) of resample_prefix.  ``M``: classes of ``per_resample`` (None: N + 1, which no hit can exceed;
+        0: not computed).  Blocking."""
+        return self._host_token_budget(self._L.scv_token_budget_prefix_i32, lambda N: N + 1, pool, tokens, truth, token_budgets, resamples, seed,
+                                       r_begin, p_offset, M, want_cells)
 
     def token_budget_wide(self, pool, tokens, truth, token_budgets, resamples: int | None = None, seed: int = 0, r_begin: int = 0,
                           p_offset: int = 0, M: int | None = None, want_cells: bool = False) -> TokenBudgetResult:
@@ -445,27 +423,8 @@ class Engine:
         ``M``: classes of ``per_resample`` (None: min(N, 1024) + 1, which no counted hit can exceed; 0: not computed).  Blocking.  On an
         ``Engine(open_domain=True)`` every int32 is a value of its own and ``cells["min_mode"]`` is a code (``decode_min_mode``); a hit that
         ties 1025 or more ways raises ScvError (ERR_ARG)."""
-        pool, _, P, N, r0, r1, _, order = _host_orderings(pool, None, resamples, r_begin, M, want_cells)
-        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-        truth = np.ascontiguousarray(truth, dtype=np.int32)
-        budgets = np.ascontiguousarray(token_budgets, dtype=np.int64)
-        if tokens.shape != pool.shape or truth.shape != (P,) or budgets.ndim != 1:
-            raise ValueError("tokens must match pool, truth must be [P] and token_budgets [B]")
-        B = budgets.shape[0]
-        R = r1 - r0
-        if M is None:
-            M = min(N, TIE_CLASSES - 1) + 1
-        tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-        tok = np.zeros((B,), dtype=np.int64)
-        votes = np.zeros((B,), dtype=np.int64)
-        tcs = np.zeros((B,), dtype=np.int64)
-        per = np.zeros((max(R, 0), B, M), dtype=np.int64) if M else None
-        cells = np.zeros((P, B), dtype=CELL_DTYPE) if want_cells else None
-        cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
-        check(self._L.scv_token_budget_wide_i32(self._ctx, _np_ptr(pool), _np_ptr(tokens), _np_ptr(budgets), _np_ptr(truth), P, B, N,
-                                                p_offset, order, r0, r1, seed, M if M else 1, _lib.MEM_HOST, _np_ptr(tie), _np_ptr(tok),
-                                                _np_ptr(votes), _np_ptr(tcs), _np_ptr(per), _np_ptr(cells), _np_ptr(cell_tokens)))
-        return TokenBudgetResult(P, R, tie, tok, votes, tcs, per, cells, cell_tokens)
+        return self._host_token_budget(self._L.scv_token_budget_wide_i32, lambda N: min(N, TIE_CLASSES - 1) + 1, pool, tokens, truth, token_budgets,
+                                       resamples, seed, r_begin, p_offset, M, want_cells)
 
     def weighted_prefix(self, pool, weights, truth, n_valid, rule: int = _lib.RULE_WEIGHT_SUM, resamples: int | None = None, seed: int = 0,
                         r_begin: int = 0, p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False) -> WeightedResult:
@@ -701,24 +660,30 @@ class Engine:
         self.use_torch_stream()
         return P, N, dev, r_end, _lib.ORDER_SHUFFLED if shuffled else _lib.ORDER_POOL, tie_class_hits, per_resample, M
 
+    def _device_resample(self, fn, budget_name, pool, truth, budgets, r_begin, r_end, seed, tokens, p_offset, tie_class_hits, token_sum, truth_count_sum,
+                         per_resample, M):
+        """The DEVICE-mode body that resample_prefix_device, resample_wide_device and iid_prefix_device share: ``fn`` is the entry of the
+        library (one argument list), ``budget_name`` names the budget argument in the messages."""
+        import torch
+        i32 = torch.int32
+        B = int(budgets.shape[0])
+        P, N, dev, _, _, tie_class_hits, per_resample, M = self._lane_device(
+            pool, B, (("truth", truth, "P", i32, True), ("tokens", tokens, "PN", i32, True), (budget_name, budgets, "B", i32, True)),
+            r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", "int64"))
+        token_sum = _device_tensor(token_sum, (B,), "token_sum", torch.int64, dev, "int64", torch.zeros) if tokens is not None else None
+        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", torch.int64, dev, "int64", torch.zeros)
+        check(fn(self._ctx, _ptr(pool), _ptr(tokens), _ptr(budgets), _ptr(truth), P, B, N, p_offset, r_begin, r_end, seed, M if M is not None else 1,
+                 _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum), _ptr(truth_count_sum), _ptr(per_resample)))
+        return tie_class_hits, token_sum, truth_count_sum, per_resample
+
     def resample_prefix_device(self, pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
                                tie_class_hits=None, token_sum=None, truth_count_sum=None, per_resample=None, M: int | None = None):
         """DEVICE-mode resample_prefix: pool / tokens torch.int32 cuda [P, N], n_valid [B], truth [P].  ACCUMULATES into the given
         int64 buffers (tie_class_hits [B, 1025], token_sum [B], truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left
         None are allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise
         (a hit with n_modes >= M is reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
-        import torch
-        i32 = torch.int32
-        B = int(n_valid.shape[0])
-        P, N, dev, _, _, tie_class_hits, per_resample, M = self._lane_device(
-            pool, B, (("truth", truth, "P", i32, True), ("tokens", tokens, "PN", i32, True), ("n_valid", n_valid, "B", i32, True)),
-            r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", "int64"))
-        token_sum = _device_tensor(token_sum, (B,), "token_sum", torch.int64, dev, "int64", torch.zeros) if tokens is not None else None
-        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", torch.int64, dev, "int64", torch.zeros)
-        check(self._L.scv_resample_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_valid), _ptr(truth), P, B, N, p_offset, r_begin, r_end,
-                                              seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum),
-                                              _ptr(truth_count_sum), _ptr(per_resample)))
-        return tie_class_hits, token_sum, truth_count_sum, per_resample
+        return self._device_resample(self._L.scv_resample_prefix_i32, "n_valid", pool, truth, n_valid, r_begin, r_end, seed, tokens, p_offset, tie_class_hits, token_sum,
+                                     truth_count_sum, per_resample, M)
 
     def resample_wide_device(self, pool, truth, n_valid, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
                              tie_class_hits=None, token_sum=None, truth_count_sum=None, per_resample=None, M: int | None = None):
@@ -727,18 +692,8 @@ class Engine:
         are allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise (a hit with
         n_modes >= M -- on an ``Engine(open_domain=True)``, where every int32 is a value of its own, also one with n_modes >= 1025 -- is
         reported by ``sync``).  Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
-        import torch
-        i32 = torch.int32
-        B = int(n_valid.shape[0])
-        P, N, dev, _, _, tie_class_hits, per_resample, M = self._lane_device(
-            pool, B, (("truth", truth, "P", i32, True), ("tokens", tokens, "PN", i32, True), ("n_valid", n_valid, "B", i32, True)),
-            r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", "int64"))
-        token_sum = _device_tensor(token_sum, (B,), "token_sum", torch.int64, dev, "int64", torch.zeros) if tokens is not None else None
-        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", torch.int64, dev, "int64", torch.zeros)
-        check(self._L.scv_resample_wide_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_valid), _ptr(truth), P, B, N, p_offset, r_begin, r_end,
-                                            seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum),
-                                            _ptr(truth_count_sum), _ptr(per_resample)))
-        return tie_class_hits, token_sum, truth_count_sum, per_resample
+        return self._device_resample(self._L.scv_resample_wide_i32, "n_valid", pool, truth, n_valid, r_begin, r_end, seed, tokens, p_offset, tie_class_hits, token_sum,
+                                     truth_count_sum, per_resample, M)
 
     def iid_prefix_device(self, pool, truth, n_draws, r_begin: int, r_end: int, seed: int, tokens=None, p_offset: int = 0,
                           tie_class_hits=None, token_sum=None, truth_count_sum=None, per_resample=None, M: int | None = None):
@@ -747,18 +702,8 @@ class Engine:
         allocated zeroed -- per_resample only when ``M`` is given).  Runs on torch's current stream, does not synchronise (a hit with
         n_modes >= M, or a budget above IID_MAX_DRAWS -- the call then computes nothing --, is reported by ``sync``).
         Returns (tie_class_hits, token_sum, truth_count_sum, per_resample)."""
-        import torch
-        i32 = torch.int32
-        B = int(n_draws.shape[0])
-        P, N, dev, _, _, tie_class_hits, per_resample, M = self._lane_device(
-            pool, B, (("truth", truth, "P", i32, True), ("tokens", tokens, "PN", i32, True), ("n_draws", n_draws, "B", i32, True)),
-            r_begin, r_end, tie_class_hits, per_resample, M, labels=("int32", "int64"))
-        token_sum = _device_tensor(token_sum, (B,), "token_sum", torch.int64, dev, "int64", torch.zeros) if tokens is not None else None
-        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", torch.int64, dev, "int64", torch.zeros)
-        check(self._L.scv_iid_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(n_draws), _ptr(truth), P, B, N, p_offset, r_begin, r_end,
-                                         seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum),
-                                         _ptr(truth_count_sum), _ptr(per_resample)))
-        return tie_class_hits, token_sum, truth_count_sum, per_resample
+        return self._device_resample(self._L.scv_iid_prefix_i32, "n_draws", pool, truth, n_draws, r_begin, r_end, seed, tokens, p_offset, tie_class_hits, token_sum,
+                                     truth_count_sum, per_resample, M)
 
     def expected_majority_device(self, pool, truth, n_valid, score=None, hit_prob=None, want_hit_prob: bool = True):
         """DEVICE-mode expected_majority: pool torch.int32 cuda [P, N], truth [P], n_valid [B] (read on the device).  OVERWRITES
@@ -782,15 +727,10 @@ class Engine:
         return score, hit_prob
 
 
-    def token_budget_prefix_device(self, pool, tokens, truth, token_budgets, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
-                                   p_offset: int = 0, tie_class_hits=None, token_sum=None, vote_count_sum=None, truth_count_sum=None,
-                                   per_resample=None, M: int | None = None, cells=None, cell_tokens=None, want_cells: bool = False):
-        """DEVICE-mode token_budget_prefix: pool / tokens torch.int32 cuda [P, N], truth [P], token_budgets torch.int64 [B].  ``r_end=None``:
-        the pool's own order (r_begin must be 0); otherwise the orderings [r_begin, r_end).  ACCUMULATES into the given int64 buffers
-        (tie_class_hits [B, 1025], token_sum, vote_count_sum, truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left None are
-        allocated zeroed -- per_resample only when ``M`` is given).  Pool order only: OVERWRITES cells (uint8 [P, B, 16]) and cell_tokens
-        (int64 [P, B]), allocated when ``want_cells``.  Runs on torch's current stream, does not synchronise.  Returns (tie_class_hits,
-        token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens)."""
+    def _device_token_budget(self, fn, pool, tokens, truth, token_budgets, r_begin, r_end, seed, p_offset, tie_class_hits, token_sum, vote_count_sum,
+                             truth_count_sum, per_resample, M, cells, cell_tokens, want_cells):
+        """The DEVICE-mode body that token_budget_prefix_device and token_budget_wide_device share: ``fn`` is the entry of the library (one
+        argument list)."""
         import torch
         i32, i64 = torch.int32, torch.int64
         B = int(token_budgets.shape[0])
@@ -804,11 +744,22 @@ class Engine:
             cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
         if want_cells or cell_tokens is not None:
             cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
-        check(self._L.scv_token_budget_prefix_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(token_budgets), _ptr(truth), P, B, N, p_offset, order,
-                                                  r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits),
-                                                  _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(per_resample), _ptr(cells),
-                                                  _ptr(cell_tokens)))
+        check(fn(self._ctx, _ptr(pool), _ptr(tokens), _ptr(token_budgets), _ptr(truth), P, B, N, p_offset, order, r_begin, r_end, seed,
+                 M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits), _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum),
+                 _ptr(per_resample), _ptr(cells), _ptr(cell_tokens)))
         return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
+
+    def token_budget_prefix_device(self, pool, tokens, truth, token_budgets, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
+                                   p_offset: int = 0, tie_class_hits=None, token_sum=None, vote_count_sum=None, truth_count_sum=None,
+                                   per_resample=None, M: int | None = None, cells=None, cell_tokens=None, want_cells: bool = False):
+        """DEVICE-mode token_budget_prefix: pool / tokens torch.int32 cuda [P, N], truth [P], token_budgets torch.int64 [B].  ``r_end=None``:
+        the pool's own order (r_begin must be 0); otherwise the orderings [r_begin, r_end).  ACCUMULATES into the given int64 buffers
+        (tie_class_hits [B, 1025], token_sum, vote_count_sum, truth_count_sum [B], per_resample [r_end - r_begin, B, M]; those left None are
+        allocated zeroed -- per_resample only when ``M`` is given).  Pool order only: OVERWRITES cells (uint8 [P, B, 16]) and cell_tokens
+        (int64 [P, B]), allocated when ``want_cells``.  Runs on torch's current stream, does not synchronise.  Returns (tie_class_hits,
+        token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens)."""
+        return self._device_token_budget(self._L.scv_token_budget_prefix_i32, pool, tokens, truth, token_budgets, r_begin, r_end, seed, p_offset, tie_class_hits,
+                                         token_sum, vote_count_sum, truth_count_sum, per_resample, M, cells, cell_tokens, want_cells)
 
     def token_budget_wide_device(self, pool, tokens, truth, token_budgets, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
                                  p_offset: int = 0, tie_class_hits=None, token_sum=None, vote_count_sum=None, truth_count_sum=None,
@@ -820,24 +771,8 @@ class Engine:
         and cell_tokens (int64 [P, B]), allocated when ``want_cells``.  One launch on torch's current stream, does not synchronise, may be
         captured into a graph (a negative token count, a hit with n_modes >= M or -- open domain -- >= 1025 is reported by ``sync``).
         Returns (tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens)."""
-        import torch
-        i32, i64 = torch.int32, torch.int64
-        B = int(token_budgets.shape[0])
-        P, N, dev, r_end, order, tie_class_hits, per_resample, M = self._lane_device(
-            pool, B, (("tokens", tokens, "PN", i32, False), ("truth", truth, "P", i32, False), ("token_budgets", token_budgets, "B", i64, False)),
-            r_begin, r_end, tie_class_hits, per_resample, M, labels=(None, None))
-        token_sum = _device_tensor(token_sum, (B,), "token_sum", i64, dev, alloc=torch.zeros)
-        vote_count_sum = _device_tensor(vote_count_sum, (B,), "vote_count_sum", i64, dev, alloc=torch.zeros)
-        truth_count_sum = _device_tensor(truth_count_sum, (B,), "truth_count_sum", i64, dev, alloc=torch.zeros)
-        if want_cells or cells is not None:
-            cells = _device_tensor(cells, (P, B, 16), "cells", torch.uint8, dev, alloc=torch.zeros)
-        if want_cells or cell_tokens is not None:
-            cell_tokens = _device_tensor(cell_tokens, (P, B), "cell_tokens", i64, dev, alloc=torch.zeros)
-        check(self._L.scv_token_budget_wide_i32(self._ctx, _ptr(pool), _ptr(tokens), _ptr(token_budgets), _ptr(truth), P, B, N, p_offset, order,
-                                                r_begin, r_end, seed, M if M is not None else 1, _lib.MEM_DEVICE, _ptr(tie_class_hits),
-                                                _ptr(token_sum), _ptr(vote_count_sum), _ptr(truth_count_sum), _ptr(per_resample), _ptr(cells),
-                                                _ptr(cell_tokens)))
-        return tie_class_hits, token_sum, vote_count_sum, truth_count_sum, per_resample, cells, cell_tokens
+        return self._device_token_budget(self._L.scv_token_budget_wide_i32, pool, tokens, truth, token_budgets, r_begin, r_end, seed, p_offset, tie_class_hits,
+                                         token_sum, vote_count_sum, truth_count_sum, per_resample, M, cells, cell_tokens, want_cells)
 
     def shortest_prefix_device(self, pool, tokens, truth, n_valid, m_keep, r_begin: int = 0, r_end: int | None = None, seed: int = 0,
                                p_offset: int = 0, tie_class_hits=None, voted_token_sum=None, spent_token_sum=None, latency_sum=None,

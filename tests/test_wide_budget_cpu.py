@@ -175,25 +175,35 @@ def test_curve_records_follow_the_mirror():
 
 
 def test_the_bench_tool_restates_the_launch_shape_of_the_header(tmp_path):
-    """tools/wide_budget_bench.py prints lanes and LDS bytes per launch from a restatement of csrc/scvote_dispatch.h: a host-only program that
-    includes the header prints the real ones (no GPU, no device code)."""
+    """The wide bench tools print lanes and LDS bytes per launch from ONE restatement of csrc/scvote_dispatch.h (tools/wide_bench.py, which
+    wide_open_bench.py and wide_budget_bench.py import): a host-only program that includes the header prints the real ones (no GPU, no
+    device code)."""
     import importlib.util
     import os
     import subprocess
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("wide_budget_bench", os.path.join(repo, "tools", "wide_budget_bench.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+
+    def load(name):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(repo, "tools", name + ".py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+    geo, tool, open_tool = load("wide_bench"), load("wide_budget_bench"), load("wide_open_bench")
     src = tmp_path / "shape.cpp"
     hdr = os.path.join(repo, "o1_inference_scaling_laws_amd", "csrc", "scvote_dispatch.h")
     src.write_text('#include "%s"\n#include <cstdio>\nint main() {\n'
                    '    for (int N : {1, 2, 3, 64, 65, 128, 129, 300, 512, 513, 1000, 1024, 1025, 2048, 4095, 4096}) for (int B : {1, 12, 13, 32}) for (int o = 0; o < 2; ++o)\n'
-                   '        printf("%%d %%d %%d %%d %%lld\\n", N, B, o, scv::wide_lanes(N), 4 * scv::wide_budget_lds_words(N, B, o != 0));\n}\n' % hdr)
+                   '        printf("%%d %%d %%d %%d %%lld %%lld\\n", N, B, o, scv::wide_lanes(N), 4 * scv::wide_budget_lds_words(N, B, o != 0),\n'
+                   '               4 * scv::wide_lds_words(N, B, o != 0));\n}\n' % hdr)
     exe = tmp_path / "shape"
     subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-std=c++17", "-O0", "-o", str(exe), str(src)],
                    check=True, stderr=subprocess.DEVNULL, timeout=300)
     rows = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.split("\n")
     rows = [tuple(int(x) for x in r.split()) for r in rows if r]
     assert len(rows) == 16 * 4 * 2
-    for N, B, o, lanes, lds in rows:
+    for N, B, o, lanes, lds, wide_lds in rows:
+        assert (geo.wide_lanes(N), 4 * geo.wide_budget_lds_words(N, B, bool(o)), 4 * geo.wide_lds_words(N, B, bool(o))) == (lanes, lds, wide_lds), (N, B, o)
         assert tool.launch_shape(N, B, bool(o))[:2] == (lanes, lds), (N, B, o)
+        assert open_tool.launch_shape(N, B, bool(o))[:2] == (lanes, wide_lds), (N, B, o)
+        if not o:
+            assert geo.launch_shape(N, B)[:2] == (lanes, wide_lds), (N, B)

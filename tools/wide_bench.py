@@ -27,14 +27,35 @@ SHAPES = {"a": (30, 1024, 1_000), "b": (30, 4096, 1_000), "c": (1_000, 1024, 100
 LDS_BYTES = 160 * 1024
 
 
-def launch_shape(N, B):
-    """(lanes, LDS bytes, workgroups per CU by LDS) of a wide launch: csrc/scvote_dispatch.h wide_pad / wide_lanes / wide_lds_words."""
+# The geometry of the wide launches, csrc/scvote_dispatch.h restated ONCE for the tools (wide_open_bench.py and wide_budget_bench.py import
+# it; tests/test_wide_budget_cpu.py holds it to the header).
+def wide_pad(N):
     n2 = 2
     while n2 < N:
         n2 <<= 1
-    lanes = min(256, max(64, n2 // 2))
-    words = 2 * n2 + 4 * B + 16 + 1024 + B * (min(N, 127) + 1) + 16 + 64 + (N + 1) // 2
-    return lanes, 4 * words, min(LDS_BYTES // (4 * words), 2048 // lanes, 32)
+    return n2
+
+
+def wide_lanes(N):
+    return min(256, max(64, wide_pad(N) // 2))
+
+
+def wide_hist_words(N, open_domain):
+    return (max(1024, N) + 1) // 2 if open_domain else 1024
+
+
+def wide_lds_words(N, B, open_domain=False):
+    return 2 * wide_pad(N) + 4 * B + 16 + wide_hist_words(N, open_domain) + B * (min(N, 127) + 1) + 16 + 64 + (N + 1) // 2
+
+
+def wide_budget_lds_words(N, B, open_domain=False):
+    return 2 * wide_pad(N) + 6 * B + 64 + 8 + wide_hist_words(N, open_domain) + B * (min(N, 127) + 1) + 16 + 64 + (N + 1) // 2
+
+
+def launch_shape(N, B):
+    """(lanes, LDS bytes, workgroups per CU by LDS) of a wide launch."""
+    lanes, lds = wide_lanes(N), 4 * wide_lds_words(N, B)
+    return lanes, lds, min(LDS_BYTES // lds, 2048 // lanes, 32)
 
 
 def timed(eng, fn, reps, between=None):

@@ -29,16 +29,12 @@ LDS_BYTES = 160 * 1024
 
 
 def launch_shape(N, B, open_domain):
-    """(lanes, LDS bytes, workgroups per CU that the LDS ALONE allows) of a launch: csrc/scvote_dispatch.h wide_pad / wide_lanes /
-    wide_budget_lds_words, restated (tests/test_wide_budget_cpu.py holds this function to the header).  The kernel's registers allow 28
-    waves per CU, 7 workgroups of 256 lanes, which is the bound where the LDS would allow more."""
-    n2 = 2
-    while n2 < N:
-        n2 <<= 1
-    lanes = min(256, max(64, n2 // 2))
-    hist = (max(N, 1024) + 1) // 2 if open_domain else 1024
-    words = 2 * n2 + 6 * B + 64 + 8 + hist + B * (min(N, 127) + 1) + 16 + 64 + (N + 1) // 2
-    return lanes, 4 * words, LDS_BYTES // (4 * words)
+    """(lanes, LDS bytes, workgroups per CU that the LDS ALONE allows) of a launch (the geometry: tools/wide_bench.py, which
+    tests/test_wide_budget_cpu.py holds to the header).  The kernel's registers allow 28 waves per CU, 7 workgroups of 256 lanes, which is
+    the bound where the LDS would allow more."""
+    from wide_bench import wide_budget_lds_words, wide_lanes
+    lds = 4 * wide_budget_lds_words(N, B, open_domain)
+    return wide_lanes(N), lds, LDS_BYTES // lds
 
 
 def drain_us(eng):

@@ -10,7 +10,7 @@ Shapes (budgets 1, 2, 4 ... N, with tokens): (a) P = 30, N = 1024, R = 10^3; (b)
 R = 10^2 (tools/wide_bench.py's); (r1) P = 10^4, N = 1024, R = 1: every item pays the encoder; (d4096) P = 30, N = 4096, R = 10^3 on a pool
 of 32-bit values with more than 1024 distinct ones per row, which only the flag-on context can take.  Kernel time from SCV_FLAG_TIMING after
 one warm-up call, median of --reps.  Every row carries the LDS bytes and the workgroups per CU of the two launches
-(csrc/scvote_dispatch.h wide_lds_words, restated here).
+(csrc/scvote_dispatch.h wide_lds_words, restated in tools/wide_bench.py).
 ``--siblings``: the flag-off wide call and the shuffle, weighted and draws-with-replacement bodies (N = 128) alone, for A/B runs of two
 builds of the library (SCV_LIB_PATH; --label names the build in the output).  Run it under `timeout`."""
 import argparse
@@ -28,14 +28,10 @@ LDS_BYTES = 160 * 1024
 
 
 def launch_shape(N, B, open_domain):
-    """(lanes, LDS bytes, workgroups per CU) of a wide launch: csrc/scvote_dispatch.h wide_pad / wide_lanes / wide_lds_words."""
-    n2 = 2
-    while n2 < N:
-        n2 <<= 1
-    lanes = min(256, max(64, n2 // 2))
-    hist = (max(1024, N) + 1) // 2 if open_domain else 1024
-    words = 2 * n2 + 4 * B + 16 + hist + B * (min(N, 127) + 1) + 16 + 64 + (N + 1) // 2
-    return lanes, 4 * words, min(LDS_BYTES // (4 * words), 28 * 64 // lanes, 32)          # 7 waves per SIMD: 28 per CU
+    """(lanes, LDS bytes, workgroups per CU) of a wide launch (the geometry: tools/wide_bench.py)."""
+    from wide_bench import wide_lanes, wide_lds_words
+    lanes, lds = wide_lanes(N), 4 * wide_lds_words(N, B, open_domain)
+    return lanes, lds, min(LDS_BYTES // lds, 28 * 64 // lanes, 32)                        # 7 waves per SIMD: 28 per CU
 
 
 def timed_pair(engs, fns, reps):
