@@ -1,6 +1,6 @@
 """CPU mirror (numpy) of scv_adaptive_prefix_i32, spec in include/scvote.h: the majority vote that samples until a stopping rule says it is
-settled.  The orderings are those of resample.py / token_budget.orderings (one definition of the shuffle).  For every prefix length the
-mirror tabulates c1 and c2 from the two largest counts (np.partition over the count vector -- the header's "second value in descending
+settled.  The orderings are those of token_budget.orderings (the one definition of the shuffle, over resample.swap_index), block by block
+through _mirror.lane_blocks.  For every prefix length the mirror tabulates c1 and c2 from the two largest counts (np.partition over the count vector -- the header's "second value in descending
 order of count", not the kernel's running runner-up) and finds each rule's stopping point as the first true entry of a condition table, not
 from a running mask of open rules: mirror and kernel arrive at n by different roads.  The rule builders (never, margin_rule, beta_rule) are
 host-only and exact integers.  The executable statement of the header text, and what the tests hold the HIP kernel to."""
@@ -12,8 +12,9 @@ from math import comb
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes, truth_codes
-from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
+from ._mirror import ERR_DOMAIN_BIT, VoteResult, check_call, dense_codes, lane_blocks, outputs, pool_shape, truth_codes, write_cells
+from .resample import MAX_N
+from .scoring import avg_tokens_used
 from .token_budget import orderings
 
 STOP_DECIDED = 0x1
@@ -55,7 +56,7 @@ def beta_rule(N: int, conf) -> np.ndarray:
 
 
 @dataclass
-class AdaptiveResult:
+class AdaptiveResult(VoteResult):
     """Integer outputs of one adaptive call + the floats derived from them.  Every denominator is P * R (cells per rule; R = 1 in pool
     order): accuracy(b) is the vote under rule b averaged over problems (and orderings), avg_votes(b) / avg_tokens_used(b) what it spent."""
     P: int
@@ -71,33 +72,17 @@ class AdaptiveResult:
     cell_votes: np.ndarray | None = None    # int32 [P, B] (pool order)
     error_bits: int = 0                 # bit 0: a vote outside 0..1023; bit 1: a hit with n_modes >= M; bit 6: an unknown rule flag
 
-    def _den(self):
-        return self.P * self.R
-
-    def accuracy(self, b: int = 0) -> float:
-        return accuracy_from_tie_classes(self.tie_class_hits[b], self._den())
-
-    def exact_accuracy(self, b: int = 0):
-        return exact_accuracy_from_tie_classes(self.tie_class_hits[b], self._den())
-
     def avg_tokens_used(self, b: int = 0) -> np.float64:
         if self.token_sum is None:
             raise ValueError("tokens were not given")
         return avg_tokens_used(self.token_sum[b], self._den())
 
     def avg_votes(self, b: int = 0) -> np.float64:
-        return np.float64(int(self.vote_count_sum[b])) / np.float64(self._den())
+        return self._mean(self.vote_count_sum[b])
 
     def stop_distribution(self, b: int = 0) -> np.ndarray:
         """share of the cells of rule b that stopped after n = 0 .. N samples: float64 [N + 1]."""
         return self.stop_hist[b].astype(np.float64) / np.float64(self._den())
-
-    def resample_accuracy(self, b: int = 0) -> np.ndarray:
-        """accuracy of every single ordering r: float64 [R]."""
-        if self.per_resample is None:
-            raise ValueError("per_resample was not requested")
-        m = np.arange(1, self.per_resample.shape[2], dtype=np.float64)
-        return (self.per_resample[:, b, 1:] / m).sum(axis=1) / self.P
 
 
 def check_rules(cap, need, rule_flags, N: int):
@@ -118,59 +103,25 @@ def adaptive_prefix(pool, truth, cap, need, rule_flags=None, tokens=None, r_begi
     """pool int32 [P, N], truth [P], cap int32 [B], need int32 [B, N + 1], rule_flags int32 [B] or None, tokens [P, N] or None.
     ``r_end=None``: pool order (one draw, r_begin must be 0); otherwise the shuffled orderings r in [r_begin, r_end).  ``M``: per_resample
     classes (None: not computed).  ``want_cells``: pool order only."""
-    pool = np.asarray(pool)
-    if pool.ndim != 2:
-        raise ValueError("pool must be [P, N]")
-    P, N = pool.shape
+    pool, P, N = pool_shape(pool)
     truth = np.asarray(truth, dtype=np.int64)
     cap, need, flags = check_rules(cap, need, rule_flags, N)
     B = cap.shape[0]
     tok = None if tokens is None else np.asarray(tokens, dtype=np.int64)
-    shuffled = r_end is not None
-    if not shuffled:
-        if r_begin != 0:
-            raise ValueError("pool order is one draw: r_begin must be 0")
-        r_end = 1
-    if not (1 <= N <= MAX_N and 1 <= B <= MAX_B and 0 <= r_begin <= r_end < 2 ** 31) or truth.shape != (P,) or \
-            (tok is not None and tok.shape != pool.shape):
-        raise ValueError(f"bad shape P={P} N={N} B={B} r=[{r_begin},{r_end})")
-    if want_cells and shuffled:
-        raise ValueError("cells are written in pool order only")
-    if M is not None and M < 1:
-        raise ValueError("M must be >= 1")
-    R = r_end - r_begin
+    shuffled, r_end, R = check_call(P, N, B, r_begin, r_end, M, MAX_N, truth.shape == (P,) and (tok is None or tok.shape == pool.shape), True, want_cells)
     nmax = np.clip(cap.astype(np.int64), 0, N)
     need = np.clip(need.astype(np.int64), 0, N + 1)
-    tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-    tsum = np.zeros(B, dtype=np.int64) if tok is not None else None
-    vsum = np.zeros(B, dtype=np.int64)
-    tcsum = np.zeros(B, dtype=np.int64)
-    hist = np.zeros((B, N + 1), dtype=np.int64)
-    per = np.zeros((R, B, M), dtype=np.int64) if M is not None else None
-    cells = cell_tokens = cell_votes = None
-    if want_cells:
-        from .engine import CELL_DTYPE
-        cells = np.zeros((P, B), dtype=CELL_DTYPE)
-        cell_tokens = np.zeros((P, B), dtype=np.int64) if tok is not None else None
-        cell_votes = np.zeros((P, B), dtype=np.int32)
     codes, uniq, bad = dense_codes(pool, open_domain)
     err = (ERR_DOMAIN_BIT if bad else 0) | (ERR_RULE_FLAG_BIT if (flags & ~STOP_DECIDED).any() else 0)
-    L = P * R
-    if L == 0:
-        return AdaptiveResult(P, R, tie, tsum, vsum, tcsum, hist, per, cells, cell_tokens, cell_votes, err)
+    tally, (tsum, vsum, tcsum), cells = outputs(P, B, R, M, 3, want_cells, err=err)
+    tsum = tsum if tok is not None else None
+    hist = np.zeros((B, N + 1), dtype=np.int64)
+    cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells and tok is not None else None
+    cell_votes = np.zeros((P, B), dtype=np.int32) if want_cells else None
     tcode = truth_codes(uniq, truth, open_domain)
     ns = np.arange(N + 1, dtype=np.int64)
-    for l0 in range(0, L, LANE_BLOCK):
-        l1 = min(L, l0 + LANE_BLOCK)
-        lanes = np.arange(l0, l1)
-        lp = lanes // R
-        lr = lanes % R                                                  # relative to r_begin
-        Lb = l1 - l0
-        if shuffled:
-            p_lo, p_hi = int(lp[0]), int(lp[-1]) + 1
-            perm = orderings(p_hi - p_lo, N, r_begin, r_end, seed, p_offset + p_lo)[(lanes - p_lo * R)]
-        else:
-            perm = np.tile(np.arange(N, dtype=np.int64), (Lb, 1))
+    for lp, lr, perm in lane_blocks(P, R, N, LANE_BLOCK, orderings, shuffled, r_begin, r_end, seed, p_offset):
+        Lb = lp.shape[0]
         x_codes = codes[lp[:, None], perm]
         S = np.zeros((Lb, N + 1), dtype=np.int64)
         if tok is not None:
@@ -206,26 +157,15 @@ def adaptive_prefix(pool, truth, cap, need, rule_flags=None, tokens=None, r_begi
             nb = cond.argmax(axis=1)
             mx, nm, tc = c1[rows, nb], nmod[rows, nb], tcs[rows, nb]
             hit = (tc > 0) & (tc == mx)
-            tie[b] += np.bincount(nm[hit], minlength=TIE_CLASSES)[:TIE_CLASSES]
+            tally.add(b, nm, hit, lr)
             tcsum[b] += int(tc.sum())
             vsum[b] += int(nb.sum())
             hist[b] += np.bincount(nb, minlength=N + 1)
             if tsum is not None:
                 tsum[b] += int(S[rows, nb].sum())
-            if per is not None:
-                m = nm[hit]
-                if (m >= M).any():
-                    err |= ERR_CLASS_BIT
-                keep = m < M
-                per[:, b, :] += np.bincount(lr[hit][keep] * M + m[keep], minlength=R * M).reshape(R, M)
             if cells is not None:
-                mc = minc[rows, nb]
-                cells["max_count"][lp, b] = mx
-                cells["truth_count"][lp, b] = tc
-                cells["n_modes"][lp, b] = nm
-                cells["min_mode"][lp, b] = [(int(c) if open_domain else int(uniq[p][c])) if n else -1 for p, c, n in zip(lp.tolist(), mc.tolist(), nb.tolist())]
-                cells["hit"][lp, b] = hit
+                write_cells(cells, lp, b, mx, tc, nm, minc[rows, nb], hit, nb > 0, None if open_domain else uniq)
                 cell_votes[lp, b] = nb
                 if cell_tokens is not None:
                     cell_tokens[lp, b] = S[rows, nb]
-    return AdaptiveResult(P, R, tie, tsum, vsum, tcsum, hist, per, cells, cell_tokens, cell_votes, err)
+    return AdaptiveResult(P, R, tally.tie, tsum, vsum, tcsum, hist, tally.per, cells, cell_tokens, cell_votes, tally.err)

@@ -1,16 +1,17 @@
 """CPU mirror (numpy) of scv_weighted_prefix_i32, spec in include/scvote.h: the weighted majority vote (rule 0: a value's weight is the sum
 of its samples' weights) and best-of-N (rule 1: the maximum) over the prefixes of a pool ordering.  The orderings are those of
-token_budget.orderings / resample.py (one definition of the shuffle).  Every prefix's W(v) is built from scratch with np.add.at /
-np.maximum.at over the prefix's samples, not by the kernel's running rule, so the two arrive at the modes by different roads.  The
-executable statement of the header text, and what the tests hold the HIP kernel to."""
+token_budget.orderings (the one definition of the shuffle, over resample.swap_index), block by block through _mirror.lane_blocks.  Every
+prefix's W(v) is built from scratch with np.add.at / np.maximum.at over the prefix's samples, not by the kernel's running rule, so the two
+arrive at the modes by different roads.  The executable statement of the header text, and what the tests hold the HIP kernel to."""
 from __future__ import annotations
 
 from dataclasses import dataclass
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, MAX_N, NUM_BINS, TIE_CLASSES, dense_codes, truth_codes
-from .scoring import accuracy_from_tie_classes, avg_tokens_used, exact_accuracy_from_tie_classes
+from ._mirror import ERR_DOMAIN_BIT, VoteResult, check_call, dense_codes, lane_blocks, outputs, pool_shape, truth_codes, write_cells
+from .resample import MAX_N
+from .scoring import avg_tokens_used
 from .token_budget import orderings
 
 RULE_WEIGHT_SUM, RULE_BEST_OF = 0, 1
@@ -20,7 +21,7 @@ LANE_BLOCK = 4096                               # lanes per block of the mirror 
 
 
 @dataclass
-class WeightedResult:
+class WeightedResult(VoteResult):
     """Integer outputs of one weighted-vote call + the floats derived from them.  Every denominator is P * R (cells per budget; R = 1 in
     pool order): accuracy(b) is the weighted vote (or best-of-N) over k_b samples averaged over problems (and orderings)."""
     P: int
@@ -32,24 +33,8 @@ class WeightedResult:
     cell_tokens: np.ndarray | None = None   # int64 [P, B] (pool order, with tokens)
     error_bits: int = 0                 # bit 0: a vote outside 0..1023; bit 1: a hit with n_modes >= M; bit 5: a weight out of range
 
-    def _den(self):
-        return self.P * self.R
-
-    def accuracy(self, b: int = 0) -> float:
-        return accuracy_from_tie_classes(self.tie_class_hits[b], self._den())
-
-    def exact_accuracy(self, b: int = 0):
-        return exact_accuracy_from_tie_classes(self.tie_class_hits[b], self._den())
-
     def avg_tokens_used(self, b: int = 0) -> np.float64:
         return avg_tokens_used(0 if self.token_sum is None else self.token_sum[b], self._den())
-
-    def resample_accuracy(self, b: int = 0) -> np.ndarray:
-        """accuracy of every single ordering r: float64 [R]."""
-        if self.per_resample is None:
-            raise ValueError("per_resample was not requested")
-        m = np.arange(1, self.per_resample.shape[2], dtype=np.float64)
-        return (self.per_resample[:, b, 1:] / m).sum(axis=1) / self.P
 
 
 def quantize_weights(scores, lo=None, hi=None) -> np.ndarray:
@@ -74,10 +59,7 @@ def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, 
                     p_offset: int = 0, M: int | None = None, tokens=None, want_cells: bool = False, open_domain: bool = False) -> WeightedResult:
     """pool / weights int32 [P, N], truth [P], n_valid int32 [B].  ``r_end=None``: pool order (one draw, r_begin must be 0); otherwise the
     shuffled orderings r in [r_begin, r_end).  ``M``: per_resample classes (None: not computed).  ``want_cells``: pool order only."""
-    pool = np.asarray(pool)
-    if pool.ndim != 2:
-        raise ValueError("pool must be [P, N]")
-    P, N = pool.shape
+    pool, P, N = pool_shape(pool)
     if weights is None:
         raise ValueError("weights are required")
     wts = np.asarray(weights, dtype=np.int64)
@@ -85,50 +67,20 @@ def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, 
     nv = np.asarray(n_valid, dtype=np.int64).reshape(-1)
     B = nv.shape[0]
     tok = None if tokens is None else np.asarray(tokens, dtype=np.int64)
-    shuffled = r_end is not None
-    if not shuffled:
-        if r_begin != 0:
-            raise ValueError("pool order is one draw: r_begin must be 0")
-        r_end = 1
-    if rule not in (RULE_WEIGHT_SUM, RULE_BEST_OF):
-        raise ValueError(f"bad rule {rule}")
-    if not (1 <= N <= MAX_N and 1 <= B <= MAX_B and 0 <= r_begin <= r_end < 2 ** 31 and p_offset >= 0) or truth.shape != (P,) \
-            or wts.shape != pool.shape or (tok is not None and tok.shape != pool.shape):
-        raise ValueError(f"bad shape P={P} N={N} B={B} r=[{r_begin},{r_end})")
-    if want_cells and shuffled:
-        raise ValueError("cells are written in pool order only")
-    if M is not None and M < 1:
-        raise ValueError("M must be >= 1")
-    R = r_end - r_begin
+    shapes_ok = p_offset >= 0 and truth.shape == (P,) and wts.shape == pool.shape and (tok is None or tok.shape == pool.shape)
+    shuffled, r_end, R = check_call(P, N, B, r_begin, r_end, M, MAX_N, shapes_ok, True, want_cells,
+                                    refusal=None if rule in (RULE_WEIGHT_SUM, RULE_BEST_OF) else f"bad rule {rule}")
     ks = np.clip(nv, 0, N)
-    tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-    tsum = np.zeros(B, dtype=np.int64) if tok is not None else None
-    per = np.zeros((R, B, M), dtype=np.int64) if M is not None else None
-    cells = cell_tokens = None
-    if want_cells:
-        from .engine import CELL_DTYPE
-        cells = np.zeros((P, B), dtype=CELL_DTYPE)
-        cells["min_mode"] = -1
-        cell_tokens = np.zeros((P, B), dtype=np.int64) if tok is not None else None
     codes, uniq, bad = dense_codes(pool, open_domain)
     wbad = (wts < 0) | (wts > WEIGHT_MAX)
     err = (ERR_DOMAIN_BIT if bad else 0) | (ERR_WEIGHT_BIT if wbad.any() else 0)
+    tally, (tsum,), cells = outputs(P, B, R, M, 1, want_cells, min_mode=-1, err=err)
+    tsum = tsum if tok is not None else None
+    cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells and tok is not None else None
     wts = wts & WEIGHT_MAX                                              # what the kernel counts after it raised the bit (results are invalid)
-    L = P * R
-    if L == 0:
-        return WeightedResult(P, R, tie, tsum, per, cells, cell_tokens, err)
     tcode = truth_codes(uniq, truth, open_domain)
-    for l0 in range(0, L, LANE_BLOCK):
-        l1 = min(L, l0 + LANE_BLOCK)
-        lanes = np.arange(l0, l1)
-        lp = lanes // R
-        lr = lanes % R                                                  # relative to r_begin
-        Lb = l1 - l0
-        if shuffled:
-            p_lo, p_hi = int(lp[0]), int(lp[-1]) + 1
-            perm = orderings(p_hi - p_lo, N, r_begin, r_end, seed, p_offset + p_lo)[(lanes - p_lo * R)]
-        else:
-            perm = np.tile(np.arange(N, dtype=np.int64), (Lb, 1))
+    for lp, lr, perm in lane_blocks(P, R, N, LANE_BLOCK, orderings, shuffled, r_begin, r_end, seed, p_offset):
+        Lb = lp.shape[0]
         x_codes = codes[lp[:, None], perm]
         x_w = wts[lp[:, None], perm]
         x_tok = None if tok is None else tok[lp[:, None], perm]
@@ -145,23 +97,13 @@ def weighted_prefix(pool, weights, truth, n_valid, rule: int = RULE_WEIGHT_SUM, 
             nm = is_mode.sum(axis=1)
             tw = np.where(tc_lane >= 0, W[rows, np.maximum(tc_lane, 0)], 0)
             hit = (tw > 0) & (tw == top)
-            tie[b] += np.bincount(nm[hit], minlength=TIE_CLASSES)[:TIE_CLASSES]
+            tally.add(b, nm, hit, lr)
             spent = None if x_tok is None else x_tok[:, :k].sum(axis=1)
             if tsum is not None:
                 tsum[b] += int(spent.sum())
-            if per is not None:
-                m = nm[hit]
-                if (m >= M).any():
-                    err |= ERR_CLASS_BIT
-                keep = m < M
-                per[:, b, :] += np.bincount(lr[hit][keep] * M + m[keep], minlength=R * M).reshape(R, M)
             if cells is not None:
-                mc = np.where(top > 0, is_mode.argmax(axis=1), -1)       # the smallest modal code: codes are value-ordered
-                cells["max_count"][lp, b] = top
-                cells["truth_count"][lp, b] = tw
-                cells["n_modes"][lp, b] = nm
-                cells["min_mode"][lp, b] = [(int(c) if open_domain else int(uniq[p][c])) if c >= 0 else -1 for p, c in zip(lp.tolist(), mc.tolist())]
-                cells["hit"][lp, b] = hit
+                mc = is_mode.argmax(axis=1)                              # the smallest modal code: codes are value-ordered
+                write_cells(cells, lp, b, top, tw, nm, mc, hit, top > 0, None if open_domain else uniq)
                 if cell_tokens is not None:
                     cell_tokens[lp, b] = spent
-    return WeightedResult(P, R, tie, tsum, per, cells, cell_tokens, err)
+    return WeightedResult(P, R, tally.tie, tsum, tally.per, cells, cell_tokens, tally.err)

@@ -1,13 +1,13 @@
 """CPU mirror (numpy) of scv_token_budget_wide_i32, spec in include/scvote.h: the majority vote over the longest prefix of an ordering of a
-pool of up to 4096 samples that fits a budget of tokens.  The orderings are those of wide.py (``wide.orderings``: one definition of the sort
-words), the result type that of token_budget.py; the prefix lengths come from ``cumsum`` plus ``searchsorted`` per ordering, not from the
+pool of up to 4096 samples that fits a budget of tokens.  The orderings are those of wide.py (``wide.orderings``: the one definition of the sort
+words; the bins of the pair are _mirror.wide_bins), the result type that of token_budget.py; the prefix lengths come from ``cumsum`` plus ``searchsorted`` per ordering, not from the
 kernel's packed words and binary search.  The executable statement of the header text, and what the tests hold the HIP kernel
 (csrc/scvote_wide_budget.hip.h) to."""
 from __future__ import annotations
 
 import numpy as np
 
-from .resample import ERR_CLASS_BIT, ERR_DOMAIN_BIT, MAX_B, NUM_BINS, TIE_CLASSES, dense_codes, truth_codes
+from ._mirror import ERR_CLASS_BIT, TIE_CLASSES, check_call, outputs, pool_shape, wide_bins, write_cells
 from .token_budget import ERR_TOKEN_BIT, ORDER_POOL, ORDER_SHUFFLED, TokenBudgetResult
 from .wide import MAX_N, orderings
 
@@ -30,55 +30,19 @@ def token_budget_wide(pool, tokens, truth, token_budgets, r_begin: int = 0, r_en
     distinct values of its row, min_mode of a cell is that rank, never error bit 0.  A hit with n_modes >= 1025 (D > 1024 only) has no column
     in tie_class_hits: it sets error bit 1 and is counted in neither table; its sums are still added.  A negative token count sets error bit
     4 and is added as 0."""
-    pool = np.asarray(pool)
-    if pool.ndim != 2:
-        raise ValueError("pool must be [P, N]")
-    P, N = pool.shape
+    pool, P, N = pool_shape(pool)
     tok = np.asarray(tokens, dtype=np.int64)
     truth = np.asarray(truth, dtype=np.int64)
     T = np.asarray(token_budgets, dtype=np.int64).reshape(-1)
     B = T.shape[0]
-    shuffled = r_end is not None
-    if not shuffled:
-        if r_begin != 0:
-            raise ValueError("pool order is one draw: r_begin must be 0")
-        r_end = 1
-    if not (1 <= N <= MAX_N and 1 <= B <= MAX_B and 0 <= r_begin <= r_end < 2 ** 31) or truth.shape != (P,) or tok.shape != pool.shape:
-        raise ValueError(f"bad shape P={P} N={N} B={B} r=[{r_begin},{r_end})")
-    if want_cells and shuffled:
-        raise ValueError("cells are written in pool order only")
-    if M is not None and M < 1:
-        raise ValueError("M must be >= 1")
-    R = r_end - r_begin
-    tie = np.zeros((B, TIE_CLASSES), dtype=np.int64)
-    tsum = np.zeros(B, dtype=np.int64)
-    vsum = np.zeros(B, dtype=np.int64)
-    tcsum = np.zeros(B, dtype=np.int64)
-    per = np.zeros((R, B, M), dtype=np.int64) if M is not None else None
-    cells = cell_tokens = None
-    if want_cells:
-        from .engine import CELL_DTYPE
-        cells = np.zeros((P, B), dtype=CELL_DTYPE)
-        cells["min_mode"] = -1
-        cell_tokens = np.zeros((P, B), dtype=np.int64)
-    err = ERR_TOKEN_BIT if (tok < 0).any() else 0
+    shuffled, r_end, R = check_call(P, N, B, r_begin, r_end, M, MAX_N, truth.shape == (P,) and tok.shape == pool.shape, True, want_cells)
+    bins, tbin, nbins, err = wide_bins(pool, truth, open_domain)
+    tally, (tsum, vsum, tcsum), cells = outputs(P, B, R, M, 3, want_cells, min_mode=-1, err=err | (ERR_TOKEN_BIT if (tok < 0).any() else 0))
+    cell_tokens = np.zeros((P, B), dtype=np.int64) if want_cells else None
     tok = np.maximum(tok, 0)                                             # (the kernel adds a negative count as 0 after raising the bit)
-    if open_domain:
-        bins, uniq, _ = dense_codes(pool, True)
-        tbin = truth_codes(uniq, truth, True)                            # the truth's bin, or -1
-        nbins = [len(u) for u in uniq]
-    else:
-        v = pool.astype(np.int64)
-        bad = (v < 0) | (v >= NUM_BINS)
-        bins = np.where(bad, NUM_BINS - 1, v)
-        tbin = np.where((truth >= 0) & (truth < NUM_BINS), truth, -1)
-        nbins = [NUM_BINS] * P
-        err |= ERR_DOMAIN_BIT if bad.any() else 0
-    if P * R == 0:
-        return TokenBudgetResult(P, R, tie, tsum, vsum, tcsum, per, cells, cell_tokens, err)
     rs = np.arange(r_begin, r_end, dtype=np.int64)
     lane = np.arange(R)
-    for p in range(P):
+    for p in range(P if R else 0):
         order = orderings(seed, p_offset + p, rs, N) if shuffled else np.arange(N, dtype=np.int64).reshape(1, N)
         tok_o = tok[p][order]                                            # [R, N] in drawing order
         S = np.zeros((R, N + 1), dtype=np.int64)
@@ -106,23 +70,14 @@ def token_budget_wide(pool, tokens, truth, token_budgets, r_begin: int = 0, r_en
             hit = live & (tc == maxc) if t >= 0 else np.zeros(R, dtype=bool)
             counted = hit
             if (nmodes[hit] >= TIE_CLASSES).any():                       # (open domain, D > 1024) no column for the class: counted nowhere
-                err |= ERR_CLASS_BIT
+                tally.err |= ERR_CLASS_BIT
                 counted = hit & (nmodes < TIE_CLASSES)
-            tie[b] += np.bincount(nmodes[counted], minlength=TIE_CLASSES)
+            tally.add(b, nmodes, counted, lane)
             tcsum[b] += int(tc[live].sum())
             tsum[b] += int(S[lane, nb].sum())
             vsum[b] += int(nb.sum())
-            if per is not None:
-                m = nmodes[counted]
-                if (m >= M).any():
-                    err |= ERR_CLASS_BIT
-                keep = m < M
-                per[:, b, :] += np.bincount(lane[counted][keep] * M + m[keep], minlength=R * M).reshape(R, M)
-            if cells is not None and live[0]:                            # pool order: R = 1
-                cells["max_count"][p, b] = maxc[0]
-                cells["truth_count"][p, b] = tc[0]
-                cells["n_modes"][p, b] = nmodes[0]
-                cells["min_mode"][p, b] = int(np.argmax(cnt[0] == maxc[0]))      # the smallest modal bin: the value, or -- open domain -- its code
-                cells["hit"][p, b] = bool(hit[0])
+            if cells is not None and live[0]:                            # pool order: R = 1; an empty cell keeps its all-zero record, min_mode -1
+                # the smallest modal bin: the value, or -- open domain -- its code
+                write_cells(cells, [p], b, maxc, tc, nmodes, [int(np.argmax(cnt[0] == maxc[0]))], hit, live)
                 cell_tokens[p, b] = S[0, nb[0]]
-    return TokenBudgetResult(P, R, tie, tsum, vsum, tcsum, per, cells, cell_tokens, err)
+    return TokenBudgetResult(P, R, tally.tie, tsum, vsum, tcsum, tally.per, cells, cell_tokens, tally.err)
